@@ -8,14 +8,18 @@ FASTA from stdin (main.c:804-808: INPUT "-") to its ordered CCS output, one
 CLI process per GPU, each over its own hole range (the 500,000 ZMWs are split
 across the N ranks: strong scaling, no collective on the data path;
 torch.distributed (gloo) only for the barrier and the max-over-ranks time).
-The timed region is process start to exit of that CLI; a "step" is 1/K of the
-rank's ZMWs (the K slices are streamed back to back by the one process), so
-ms_per_step x steps is the whole pass.  The FASTA is generated before the
-timed region (tools/synth_fa); the CCS are read back through a FIFO, checked
-for count and input order, and a sample is compared byte for byte with the
-oracle in the cpu_baseline leg (outside the timed region).
+The timed region is process start to exit of that CLI; a "step" is --e-zmws
+config-E ZMWs (25,000: --steps 20 is the whole of config E), and the K steps
+are streamed back to back by the one process, so ms_per_step x steps is the
+whole pass.  The FASTA is generated before the timed region (tools/synth_fa);
+the CCS are read back through a FIFO and checked for count and input order.
+A plain run does this and nothing else.  --dump-outputs DIR then writes what
+the last step returned (dump_outputs: every CCS length, and a seeded sample
+of the CCS themselves) as DIR/*.npy; the same arguments give the same inputs.
 
-Beside it, on the same device:
+With --full a sample of the CCS is also compared byte for byte with the
+oracle in the cpu_baseline leg (outside the timed region), and beside the
+headline, on the same device:
   * `roofline`: the dominant kernel (the solo object of ccsx_zmw_kernel) on
     16,384 config-E ZMWs per launch, inputs resident in HBM, HIP events on the
     launch stream (DESIGN.md §6);
@@ -30,7 +34,8 @@ Beside it, on the same device:
 Each rank's CLI and generator get the node's CPU share / LOCAL_WORLD_SIZE
 threads, bound to a disjoint CPU slice when N > 1 (rank_cpus).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config B|C|D|E|H|HP] [--e-zmws 0]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--config B|C|D|E|H|HP] [--e-zmws 0]
 
 --e-zmws 0 makes the kernel line of --config the headline (A/B sessions).
 Prints ONE JSON line (rank 0).  See DESIGN.md §6 and profiles/.
@@ -38,6 +43,7 @@ Prints ONE JSON line (rank 0).  See DESIGN.md §6 and profiles/.
 from __future__ import annotations
 
 import argparse
+import atexit
 import json
 import os
 import random
@@ -71,11 +77,12 @@ CONFIGS = {
     "E": dict(workload="E-slice: 2000 ZMWs per GPU, insert ~U[5,25] kb x passes ~U[5,12] (total <= 450 kb), "
                        "10% error, shredded mode", nzmw=2000, L=0, passes=0, mode=0),
 }
-E_WORKLOAD = ("E: 500,000 synthetic ZMWs, insert ~U[5,25] kb x passes ~U[5,12] (total <= 450 kb), 10% error, "
+E_WORKLOAD = ("E: {zmws:,} synthetic ZMWs, insert ~U[5,25] kb x passes ~U[5,12] (total <= 450 kb), 10% error, "
               "subread FASTA on stdin through the ccsx CLI (-A, shredded mode), CCS in input order")
 SEED = 20201104
 MODE_SHRED = 0
 E_HOLE0 = 20_000_000       # config E's holes (the CLI headline)
+E_STEP_ZMWS = 25_000       # one step of the CLI headline: --steps 20 is config E's 500,000 ZMWs
 E_LAUNCH_HOLE0 = 10_000_000  # the roofline / e2e lines' config-E holes
 # gfx950 integer VALU: 256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6e12 int32 lane-ops/s
 # (MI355X_MICROARCH.md: SIMD-32, wave64 in 2 cycles); 10 int ops per DP cell
@@ -85,6 +92,7 @@ OPS_PER_CELL = 10
 CLI = os.path.join(ROOT, "ccsx_amd", "bin", "ccsx")
 ORIG_AFFINITY = os.sched_getaffinity(0)  # restored after a rank's CLI ran bound to its slice
 SYNTH_FA = os.path.join(ROOT, "tools", "synth_fa")
+T_START = time.perf_counter()  # the CLI headline's timed run starts --settle seconds after this at the earliest
 
 
 def rank_holes(cfg: dict, rank: int) -> range:
@@ -228,8 +236,9 @@ def rank_cpus(local: int, local_world: int, share: int | None = None, affinity=N
 
 def read_records(path, want: set, scan: dict):
     """Read a CCS FASTA (a FIFO while the CLI writes it): record count, input
-    (hole) order, and the sequences of the holes in `want`."""
-    got, nrec, in_order, last, cur, nb = {}, 0, True, -1, None, 0
+    (hole) order, the length of every record's line in input order, and the
+    sequences of the holes in `want`."""
+    got, nrec, in_order, last, cur, nb, lens = {}, 0, True, -1, None, 0, []
     with open(path, "rb") as f:
         for line in f:
             nb += len(line)
@@ -239,9 +248,52 @@ def read_records(path, want: set, scan: dict):
                 in_order &= h > last
                 last = h
                 cur = h if h in want else None
-            elif cur is not None:
-                got[cur] = line.rstrip(b"\n")
-    scan.update(got=got, nrec=nrec, in_order=in_order, bytes=nb)
+                lens.append(0)
+            else:
+                lens[-1] += len(line) - 1
+                if cur is not None:
+                    got[cur] = line.rstrip(b"\n")
+    scan.update(got=got, nrec=nrec, in_order=in_order, bytes=nb, lens=lens)
+
+
+DUMP_SAMPLE = 256          # CCS kept whole by --dump-outputs (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_sample(ids, k: int = DUMP_SAMPLE):
+    """The ids (holes, or batch indices) whose CCS --dump-outputs keeps whole:
+    a seeded sample, the same for the same ids."""
+    ids = list(ids)
+    return sorted(random.Random(SEED).sample(ids, min(k, len(ids))))
+
+
+def dump_outputs(out_dir: str, ids, ccs_of: dict, lens) -> dict:
+    """--dump-outputs: what the last timed step returned, as .npy arrays:
+      ccs_len.npy      float64  length of every CCS of the step, in output order
+      sample_ids.npy   float64  ids (holes / batch indices) of the sampled ZMWs
+      sample_len.npy   float64  their CCS lengths
+      sample_ccs.npy   float32  their CCS back to back, one ASCII code per base
+    The sample is cut where the files would pass DUMP_MAX_BYTES in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    all_len = np.asarray(list(lens), dtype=np.float64)
+    room = DUMP_MAX_BYTES - all_len.nbytes - (1 << 16)
+    kept, seqs = [], []
+    for i in ids:
+        s = ccs_of[i]
+        need = 4 * len(s) + 16
+        if need > room:
+            break
+        room -= need
+        kept.append(i)
+        seqs.append(np.frombuffer(s, dtype=np.uint8))
+    files = {"ccs_len": all_len,
+             "sample_ids": np.asarray(kept, dtype=np.float64),
+             "sample_len": np.asarray([len(s) for s in seqs], dtype=np.float64),
+             "sample_ccs": (np.concatenate(seqs) if seqs else np.zeros(0, np.uint8)).astype(np.float32)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.size) for name, a in files.items()}
 
 
 def run_cli(inp, n_zmw: int, want: set, env: dict, threads: int, log_path: str, gen_cmd=None):
@@ -278,6 +330,8 @@ def run_cli(inp, n_zmw: int, want: set, env: dict, threads: int, log_path: str, 
         os.remove(fifo)
         os.rmdir(d)
     if r.returncode != 0:
+        with open(log_path, errors="replace") as log:  # the log may be in a directory removed at exit
+            sys.stderr.write(log.read()[-4000:])
         raise SystemExit(f"ccsx exited {r.returncode} (log {log_path})")
     if scan.get("nrec") != n_zmw or not scan.get("in_order"):
         raise SystemExit(f"ccsx output: {scan.get('nrec')} records for {n_zmw} ZMWs, in order {scan.get('in_order')}")
@@ -362,9 +416,12 @@ def cli_line(args, rank: int, world: int, local: int, local_world: int, ndev: in
     rank's CLI and generator get its share of the node's CPUs (rank_cpus),
     bound to its own CPU slice when several ranks share the node.  Returns
     (result, input path or None, temp dir): the input is kept for the
-    one-process line (the caller removes the temp dir)."""
-    holes = e_rank_range(args.e_zmws, rank, world)
+    one-process line (the caller removes the temp dir).  The run is --steps
+    steps of --e-zmws ZMWs (over all ranks), streamed back to back through
+    the one timed process."""
+    holes = e_rank_range(args.e_zmws * args.steps, rank, world)
     n = len(holes)
+    last_step = holes[n - max(1, n // args.steps):]  # this rank's part of the last step
     threads, cpus = rank_cpus(local, local_world)
     if cpus:
         # children inherit the binding (no preexec_fn: the FIFO reader is a thread)
@@ -400,11 +457,22 @@ def cli_line(args, rank: int, world: int, local: int, local_world: int, ndev: in
         res["gen_s"] = round(time.perf_counter() - t0, 3)
         res["input"] = "generator pipe" if pipe else "file on stdin"
         rnd = random.Random(holes.start ^ n)
-        sample = sorted(rnd.sample(list(holes), min(args.e_sample, n))) if rank == 0 else []
+        # the holes compared with the oracle afterwards (--full), and the
+        # ones --dump-outputs writes out
+        sample = sorted(rnd.sample(list(holes), min(args.e_sample, n))) if rank == 0 and args.full else []
+        dumped = dump_sample(last_step) if rank == 0 and args.dump_outputs else []
+        # untimed: the device memory that the warmup CLI, or a run just before
+        # this one, released is cleared for seconds after, reported free while
+        # it still is (launches then run at half their rate); config E's
+        # 500,000 ZMWs take longer than that to generate, a few steps' do not
+        settle = args.settle - (time.perf_counter() - T_START)
+        if settle > 0:
+            time.sleep(settle)
+        res["settle_s"] = round(max(0.0, settle), 3)
         if dist is not None:
             dist.barrier()
         log = os.path.join(out_dir, f"cli_r{rank}.log")
-        dt, scan = run_cli(fa, n, set(sample), env, threads, log, gen_cmd=gen if pipe else None)
+        dt, scan = run_cli(fa, n, set(sample) | set(dumped), env, threads, log, gen_cmd=gen if pipe else None)
         if dist is not None:
             dist.barrier()
         res["cli_s"] = round(dt, 3)
@@ -415,6 +483,8 @@ def cli_line(args, rank: int, world: int, local: int, local_world: int, ndev: in
         res["timeline"] = cli_timeline(log)
         res["sample_holes"] = sample
         res["sample_got"] = scan["got"]
+        if dumped:
+            res["dumped"] = dump_outputs(args.dump_outputs, dumped, scan["got"], scan["lens"][-len(last_step):])
     except BaseException:
         shutil.rmtree(tmp, ignore_errors=True)
         raise
@@ -481,7 +551,8 @@ def one_process_line(args, world: int, parts, sample, out_dir: str, tmp: str, lo
     output checked for count and input order and the same sampled holes kept
     for the oracle comparison."""
     share, _, _ = cpu_share()
-    res = {"zmws": args.e_zmws, "jobs": share, "ngpu": world}
+    total = args.e_zmws * args.steps
+    res = {"zmws": total, "jobs": share, "ngpu": world}
     if local_world is not None and local_world != world:
         # the ranks' inputs are files on their own nodes: one process on rank
         # 0's node cannot read them (ADVICE r5)
@@ -507,10 +578,10 @@ def one_process_line(args, world: int, parts, sample, out_dir: str, tmp: str, lo
     res["mem_free_frac"] = mw.get("free_frac")
     res["mem_wait_ok"] = mw["ok"]
     try:
-        dt, scan = run_cli(full, args.e_zmws, set(sample), env, share, log)
+        dt, scan = run_cli(full, total, set(sample), env, share, log)
     finally:
         os.remove(full)
-    res.update({"cli_s": round(dt, 3), "value": round(args.e_zmws / dt, 3), "unit": "ZMWs/s",
+    res.update({"cli_s": round(dt, 3), "value": round(total / dt, 3), "unit": "ZMWs/s",
                 "records": scan["nrec"], "records_in_input_order": scan["in_order"], "cells": cli_cells(log),
                 "timeline": cli_timeline(log), "sample_got": scan["got"]})
     return res
@@ -634,7 +705,8 @@ def kernel_line(eng, cfg: dict, zs, steps: int, warmup: int, dist):
                          "frac_vs_packed_int16": round(achieved / (2 * VALU_PEAK_TOPS), 5),
                          "kernel": "ccsx_zmw_kernel", "avg_launch_ms": round(avg_launch_s * 1e3, 3),
                          "ops_per_cell": OPS_PER_CELL, "kernel_cfg": eng.kernel_cfg()},
-            "step_ms": [round(k, 3) for k in kernel_ms]}
+            "step_ms": [round(k, 3) for k in kernel_ms],
+            "ccs": [r[0] for r in res]}  # the last launch's CCS (the caller takes them out of the line)
 
 
 def e2e_line(eng, batch, n: int, dist, keep):
@@ -715,8 +787,17 @@ def main():
     ap.add_argument("--config", default="B", choices=sorted(CONFIGS), help="the kernel line's configuration")
     ap.add_argument("--nzmw", type=int, default=0, help="override the kernel line's ZMWs per GPU (testing only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--e-zmws", type=int, default=500_000,
-                    help="config E ZMWs of the CLI headline, over all ranks (0: the kernel line is the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the roofline, kernel, end-to-end and one-process lines, the oracle "
+                         "check of a sample and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--e-zmws", type=int, default=E_STEP_ZMWS,
+                    help="config E ZMWs per step of the CLI headline, over all ranks: the run is --steps times "
+                         "as many (0: the kernel line is the headline)")
+    ap.add_argument("--settle", type=float, default=15.0,
+                    help="the CLI headline's timed run starts this many seconds after bench.py at the earliest "
+                         "(untimed; generating 20 steps of input takes longer anyway)")
     ap.add_argument("--e-sample", type=int, default=1000, help="sampled config-E holes checked against the oracle")
     ap.add_argument("--roofline-zmws", type=int, default=16384,
                     help="config-E ZMWs per launch of the roofline line (0: skip; the kernel line's roofline)")
@@ -725,10 +806,24 @@ def main():
     ap.add_argument("--kcfg", type=int, default=-1, help="force a kernel configuration (0 latency, 1 occupancy, 3 solo, "
                                                          "2 throughput; -1: by slice size)")
     ap.add_argument("--wg-cap", type=int, default=0, help="measurement: at most this many workgroups per CU (0: off)")
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "gpurun_out", "bench"), help="CLI logs")
+    ap.add_argument("--out-dir", default=None,
+                    help="keep the CLI logs here (default: a temporary directory, removed at exit; the "
+                         "repository itself may be read-only)")
     ap.add_argument("--no-one-process", dest="one_process", action="store_false",
                     help="N > 1: skip rank 0's one-process line (one CLI over all N GPUs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run measures the headline alone: the CLI line, or with
+        # --e-zmws 0 the kernel line (with --no-kernel-line, the roofline line)
+        args.e2e_zmws = 0
+        args.one_process = False
+        args.no_cpu_baseline = True
+        if args.e_zmws:
+            args.no_kernel_line = True
+        if args.e_zmws or not args.no_kernel_line:
+            args.roofline_zmws = 0
     cfg = dict(CONFIGS[args.config])
     if args.nzmw:
         cfg["nzmw"] = args.nzmw
@@ -753,7 +848,11 @@ def main():
             sys.stdout.flush()
             os.dup2(saved, 1)
             os.close(saved)
-    os.makedirs(args.out_dir, exist_ok=True)
+    if args.out_dir is None:
+        args.out_dir = tempfile.mkdtemp(prefix="ccsx_bench_logs_")
+        atexit.register(shutil.rmtree, args.out_dir, ignore_errors=True)
+    else:
+        os.makedirs(args.out_dir, exist_ok=True)
 
     import ccsx_amd as cx
     import ccsx_amd.native as nat
@@ -766,12 +865,13 @@ def main():
         raise SystemExit("bench.py: no HIP device visible")
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     sharing = (local_world + ndev - 1) // ndev
-    eng = cx.Engine(local % ndev)
-    if sharing > 1:
+    # the launch lines' context (none where only the CLI line runs)
+    eng = cx.Engine(local % ndev) if zs is not None or args.roofline_zmws or args.e2e_zmws else None
+    if eng is not None and sharing > 1:
         eng.set_mem_share(sharing)
-    if args.kcfg >= 0:
+    if eng is not None and args.kcfg >= 0:
         eng.set_kernel_cfg(args.kcfg)
-    if args.wg_cap:
+    if eng is not None and args.wg_cap:
         eng.set_wg_cap(args.wg_cap)
     overrides = {k: os.environ[k] for k in ("CCSX_LIB",) if os.environ.get(k)}
     if args.wg_cap:
@@ -780,8 +880,12 @@ def main():
 
     # config B (or --config): K launches, inputs resident
     kline = None
+    dumped = None
     if zs is not None:
         kline = kernel_line(eng, cfg, zs, args.steps, args.warmup, dist)
+        ccs = kline.pop("ccs")
+        if args.dump_outputs and not args.e_zmws and rank == 0:  # the headline of this run
+            dumped = dump_outputs(args.dump_outputs, dump_sample(range(len(ccs))), ccs, map(len, ccs))
         kline["traffic"] = traffic_entry(traffic_key(args.config, args.nzmw), kline["cells_per_step"])
         kline["workload"] = cfg["workload"]
     # the dominant kernel of the headline workload: config-E ZMWs per launch,
@@ -793,13 +897,18 @@ def main():
                                E_LAUNCH_HOLE0 + (rank + 1) * args.roofline_zmws), min(threads, 16))
         eng.stage_batch(ebatch, MODE_SHRED)
         ecfg = dict(nzmw=args.roofline_zmws, mode=MODE_SHRED)
-        rsteps = max(1, min(args.steps, 5))
+        # beside another headline at most 5 launches; as the headline, --steps of them
+        headline = zs is None and not args.e_zmws
+        rsteps = args.steps if headline else min(args.steps, 5)
         for _ in range(min(args.warmup, 1)):
             eng.launch(MODE_SHRED)
         ms = [eng.launch(MODE_SHRED) for _ in range(rsteps)]
         res = eng.fetch()
         if any(r[1] != 0 for r in res):
             raise SystemExit("roofline line: device status != 0")
+        if args.dump_outputs and headline and rank == 0:
+            dumped = dump_outputs(args.dump_outputs, dump_sample(range(len(res))), [r[0] for r in res],
+                                  (len(r[0]) for r in res))
         cells = sum(r[2] for r in res)
         avg = sum(ms) / len(ms) / 1e3
         achieved = cells * OPS_PER_CELL / avg / 1e12
@@ -820,7 +929,8 @@ def main():
         e2e_keep = sorted(random.Random(7 + rank).sample(range(args.e2e_zmws), min(64, args.e2e_zmws)))
         e2e, e2e_kept = e2e_line(eng, b2, args.e2e_zmws, dist, e2e_keep)
         e2e_holes = [E_LAUNCH_HOLE0 + rank * args.e2e_zmws + i for i in e2e_keep]
-    eng.close()
+    if eng is not None:
+        eng.close()
     del ebatch
 
     cli = None
@@ -841,7 +951,8 @@ def main():
                         one = one_process_line(args, world, parts, cli["sample_holes"], args.out_dir, tmp,
                                                local_world=local_world, ndev=ndev)
                     except Exception as e:  # noqa: BLE001
-                        one = {"zmws": args.e_zmws, "ngpu": world, "error": f"{type(e).__name__}: {e}"[:400]}
+                        one = {"zmws": args.e_zmws * args.steps, "ngpu": world,
+                               "error": f"{type(e).__name__}: {e}"[:400]}
                 dist.barrier()
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
@@ -849,29 +960,33 @@ def main():
     if rank == 0:
         out = {"metric": "CCS ZMWs/sec (whole node)"}
         if cli is not None:
-            value = args.e_zmws / cli_s
+            total = args.e_zmws * args.steps
+            value = total / cli_s
             out.update({
                 "value": round(value, 3), "unit": "ZMWs/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(cli_s / args.steps * 1e3, 3), "higher_is_better": True,
                 "scaling": "strong", "vs_baseline": None, "dtype": "int32",
                 "data": "synthetic (SURVEY.md §8d generator, seed 20201104, per-rank hole ranges)",
-                "config": {"workload": E_WORKLOAD, "zmws": args.e_zmws, "insert_len": "5000-25000", "passes": "5-12",
+                "config": {"workload": E_WORKLOAD.format(zmws=total), "zmws": total, "zmws_per_step": args.e_zmws,
+                           "insert_len": "5000-25000", "passes": "5-12",
                            "mode": "shredded", "parallelism": f"hole-range sharding x{world}, one CLI per GPU, "
                                                               "no collectives",
-                           "step": f"1/{args.steps} of each rank's config-E ZMWs; the CLI streams the {args.steps} "
-                                   "slices back to back in one process, timed from its start to its exit",
+                           "step": f"{args.e_zmws} config-E ZMWs (each rank its share of them); the CLI streams "
+                                   f"the {args.steps} steps back to back in one process, timed from its start "
+                                   "to its exit",
                            "cli_jobs": cli["jobs"], "cli_cpus": cli["cpus"]},
-                # steps / ms_per_step are nominal: ONE CLI process per rank is
-                # timed from its start to its exit, and ms_per_step x steps is
-                # that whole time (no per-step clock); warmup = one separate,
+                # --steps sets the work: ONE CLI process per rank runs steps x
+                # --e-zmws ZMWs and is timed from its start to its exit (no
+                # per-step clock: ms_per_step is that time / steps, the process's
+                # start and exit shared among the steps); warmup = one separate,
                 # smaller CLI run (warmup x 1,024 ZMWs) before the input is made
-                "steps_nominal": True,
-                "timed_region": "one ccsx process per rank, start to exit (max over ranks); "
+                "timed_region": "one ccsx process per rank over all the steps, start to exit (max over ranks); "
                                 "ms_per_step = that time / steps",
                 "gcups": round(cells_all / cli_s / 1e9, 3),
                 "cli": {k: v for k, v in cli.items() if k not in ("sample_holes", "sample_got")},
             })
-            out["roofline"] = rline if rline is not None else kline["roofline"] if kline is not None else None
+            if args.full:
+                out["roofline"] = rline if rline is not None else kline["roofline"] if kline is not None else None
             if kline is not None:
                 out["kernel_B" if args.config == "B" else f"kernel_{args.config}"] = kline
         elif kline is None:
@@ -909,8 +1024,10 @@ def main():
             out["config"]["overrides"] = overrides
         if e2e is not None:
             out["e2e"] = e2e
+        if dumped is not None:
+            out["dumped"] = dumped
         # the checker / CPU leg (outside every timed region)
-        if not args.no_cpu_baseline or cli is not None or e2e is not None:
+        if args.full and (not args.no_cpu_baseline or cli is not None or e2e is not None):
             from ccsx_amd import synth_zmw
             from oracle.oracle import prepare as oracle_prepare  # the checker's own ccs_prepare
             if e2e is not None:
@@ -933,7 +1050,7 @@ def main():
                     out["cpu_baseline"] = cb
         print(json.dumps(out), flush=True)
         bad = []
-        if cli is not None and out["cli"]["sample_equal"] != out["cli"]["sample"]:
+        if cli is not None and out["cli"].get("sample_equal") != out["cli"].get("sample"):
             bad.append("CLI sample")
         op = out.get("one_process", {})
         if "sample" in op and op["sample_equal"] != op["sample"]:

@@ -76,8 +76,9 @@ def test_bench_two_ranks_on_device():
     JSON line; the config-E headline split over the ranks' CLIs (each over
     its own hole range, its device share halved) with the sample checked
     against the oracle; the e2e line's gather."""
-    small = ["--steps", "2", "--warmup", "1", "--nzmw", "96", "--e2e-zmws", "64", "--no-cpu-baseline",
-             "--e-zmws", "600", "--e-sample", "12", "--roofline-zmws", "128"]
+    # --full: every line beside the headline; 2 steps of 300 config-E ZMWs, no settling time
+    small = ["--full", "--settle", "0", "--steps", "2", "--warmup", "1", "--nzmw", "96", "--e2e-zmws", "64", "--no-cpu-baseline",
+             "--e-zmws", "300", "--e-sample", "12", "--roofline-zmws", "128"]
     one = _run_bench(1, small)
     two = _run_bench(2, small)
     import ccsx_amd.native as nat
@@ -214,6 +215,6 @@ def test_one_process_line_devices_and_multi_node_skip(tmp_path):
     import types
     assert bench.one_process_devices(8, 8) == list(range(8))
     assert bench.one_process_devices(2, 1) == [0]
-    args = types.SimpleNamespace(e_zmws=1000)
+    args = types.SimpleNamespace(e_zmws=1000, steps=1)
     res = bench.one_process_line(args, 16, [None] * 16, [], str(tmp_path), str(tmp_path), local_world=8, ndev=8)
     assert "multi-node" in res["skipped"]

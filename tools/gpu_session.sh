@@ -54,7 +54,7 @@ step() {
       local rc=$?; tail -3 "$OUT/parity${CCSX_LIB:+_$CCSX_LIB}.log"; return $rc ;;
     bench)
       if [ -z "$cfg" ]; then
-        timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json"
+        timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json"
         return $?
       fi
       local f="$OUT/bench_${cfg}${k:+_k$k}${CCSX_LIB:+_${CCSX_LIB%.so}}${CCSX_WG_PER_CU:+_w$CCSX_WG_PER_CU}.json"
@@ -99,7 +99,7 @@ step() {
       done ;;
     e2e)  # e2e:N[:KCFG] -- bench.py's config-E end-to-end line on N ZMWs (CCSX_KCFG forces a kernel cfg)
       local f="$OUT/e2e_${cfg}${k:+_k$k}${CCSX_SHRED_READ_CAP:+_rc$CCSX_SHRED_READ_CAP}.json"
-      CCSX_KCFG=${k:--1} CCSX_TIMING=1 timeout -k 10 600 python -u bench.py --steps 1 --warmup 0 --no-cpu-baseline \
+      CCSX_KCFG=${k:--1} CCSX_TIMING=1 timeout -k 10 600 python -u bench.py --full --steps 1 --warmup 0 --no-cpu-baseline \
         --e2e-zmws "$cfg" > "$f" 2> "${f%.json}.err" &&
         python3 -c "import json,sys; d=json.load(open(sys.argv[1]))['e2e']; print(sys.argv[1], d['value'], 'ZMWs/s', d['s'], 's', d['gcups'], 'GCUPS', 'first', d['first_call_s'])" "$f" ;;
     kt)
@@ -134,7 +134,7 @@ step() {
       local rc=$?; tail -2 "$OUT/ingest_$cfg.log"; return $rc ;;
     n2)  # n2:EZMWS -- the driver's two-rank launch on this box (torch.distributed.run, both ranks on its GPU)
       timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 --steps 4 --warmup 1 --e-zmws "$cfg" --e-sample 100 \
+        --master-port 29517 bench.py --full --gpus 2 --steps 4 --warmup 1 --e-zmws "$((cfg / 4))" --e-sample 100 \
         --nzmw 200 --roofline-zmws 1024 --e2e-zmws 1024 \
         --out-dir "$OUT/n2" > "$OUT/bench_n2.json" 2> "$OUT/bench_n2.err"
       local rc=$?; cat "$OUT/bench_n2.json"; return $rc ;;
