@@ -188,6 +188,9 @@ struct Slot {
     uint64_t seq_bytes = 0, ws_bytes = 0, out_bytes = 0, msa_bytes = 0, bp_words = 0;
     uint32_t nseg_total = 0;
     bool inflight = false;             // launched, results not fetched yet
+    // staged with a quality plane (ccsx_gpu_set_quality): out_bytes more behind
+    // the CCS plane in d_out and h_out, a byte per CCS byte at the same offsets
+    bool qual = false;
     std::vector<ccsx::ZmwDesc> desc;
     std::vector<uint32_t> hoff, hlen, order;  // host copies the async H2D reads from
     DevBuf d_prof, d_bp;
@@ -248,6 +251,12 @@ struct ccsx_ctx {
     uint64_t mem_waits = 0, mem_replans = 0;  // slices that waited for memory / were cut below the plan
     bool prealloc = false;             // reserve the slice budget up front
     bool bp_log = false;               // record the -v >= 3 breakpoint log (main.c:619-620)
+    bool quality = false;              // stage a quality plane beside the CCS (ccsx_gpu_set_quality)
+    // ccsx_gpu_quality(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
+    int last_qual = 0;
+    std::vector<uint8_t> run_qual;     // ccsx_gpu_run's gathered qualities (run_arena's offsets)
+    std::vector<uint64_t> run_qoff;    // per ZMW of the call: offset into run_qual
+    std::vector<uint32_t> run_qlen;    // per ZMW of the call: quality bytes (0: no CCS)
     std::vector<uint32_t> run_bp;      // ccsx_gpu_run: the gathered logs, (i, ncols) pairs
     std::vector<uint64_t> run_bp_off;  // per ZMW of the call: offset into run_bp (pairs)
     std::vector<uint32_t> run_bp_n;    // per ZMW of the call: rounds
@@ -260,6 +269,11 @@ struct ccsx_ctx {
         size_t nz = 0;
         int64_t fault = -1;            // test hook, taken from ccsx_gpu_set_fault at submit
         std::vector<uint8_t> arena;    // the collected batch's CCS strings
+        bool qual = false;             // submitted with quality on
+        bool has_qual = false;         // collected, and qarena / qoff / qlen hold its qualities
+        std::vector<uint8_t> qarena;   // the collected batch's qualities (arena's offsets)
+        std::vector<uint64_t> qoff;
+        std::vector<uint32_t> qlen;
     } tk[2];
 };
 
@@ -410,7 +424,8 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::zcaps(d, S, lmax, zi.nseg, full, c->tight_rows, shred_win, c->tight_out, c->tight_far);
     ccsx::ZLayout L;
     ccsx::zlayout(L, d);
-    return ccsx::align256(L.total) + hi + d.outcap + uint64_t(zi.nseg) * 8 + sizeof(ccsx::ZmwDesc) + 32;
+    return ccsx::align256(L.total) + hi + d.outcap + (c->quality ? d.outcap : 0u) + uint64_t(zi.nseg) * 8 +
+           sizeof(ccsx::ZmwDesc) + 32;
 }
 
 // The bytes a slice staged into slot s may need now: the device's free memory
@@ -501,6 +516,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     s.seq_bytes = seq_b, s.ws_bytes = ws_b, s.out_bytes = out_b, s.msa_bytes = msa_b;
     s.bp_words = bp_w;
     s.nseg_total = nseg;
+    s.qual = c->quality && !with_msa;
+    const uint64_t qual_b = s.qual ? out_b : 0;
     // 2-bit read buffer (ccsx_kernel.hip stage_read); at least one band:
     // every lane reads its window bytes even when the read is shorter.  A
     // slice with a read or a cursor array beyond the LDS budget runs the
@@ -556,7 +573,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
+    const uint64_t need = seq_b + ws_b + out_b + qual_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
         // already cut the slice to what is free; a submitted batch cannot be cut)
@@ -582,7 +599,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, s.d_desc.reserve(nz * sizeof(ccsx::ZmwDesc)));
     HIPCHK(c, s.d_order.reserve(nz * 4));
     HIPCHK(c, s.d_ws.reserve(ws_b));
-    HIPCHK(c, s.d_out.reserve(out_b));
+    HIPCHK(c, s.d_out.reserve(out_b + qual_b));
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
     HIPCHK(c, s.d_ncols.reserve(nz * 4));
@@ -707,6 +724,7 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     a.lds_nmax = s.lds_nmax;
     a.prof = nullptr;
     a.bplog = s.bp_words ? s.d_bp.as<uint32_t>() : nullptr;
+    a.qual = s.qual ? s.d_out.as<uint8_t>() + s.out_bytes : nullptr;
     if (c->profiling) {
         HIPCHK(c, s.d_prof.reserve(s.nz * ccsx::kProfSlots * 8));
         a.prof = s.d_prof.as<unsigned long long>();
@@ -730,7 +748,8 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
 {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nz = s.nz;
-    HIPCHK(c, s.h_out.reserve(s.out_bytes, c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
+    const uint64_t planes = s.qual ? 2 : 1;  // the quality plane follows the CCS plane, one copy for both
+    HIPCHK(c, s.h_out.reserve(s.out_bytes * planes, c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
     s.h_olen.resize(nz);
     s.h_status.resize(nz);
     s.h_cells.resize(nz);
@@ -739,7 +758,7 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
         HIPCHK(c, hipMemcpyAsync(s.h_olen.data(), s.d_olen.p, nz * 4, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipMemcpyAsync(s.h_status.data(), s.d_status.p, nz * 4, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipMemcpyAsync(s.h_cells.data(), s.d_cells.p, nz * 8, hipMemcpyDeviceToHost, s.stream));
-        HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes, hipMemcpyDeviceToHost, s.stream));
+        HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes * planes, hipMemcpyDeviceToHost, s.stream));
         if (s.bp_words)
             HIPCHK(c, hipMemcpyAsync(s.h_bp.data(), s.d_bp.p, s.bp_words * 4, hipMemcpyDeviceToHost, s.stream));
     }
@@ -774,6 +793,7 @@ int ccsx_gpu_stage_ex(ccsx_ctx *c, const ccsx_zmw_in *z, size_t nz, int with_msa
         HIPCHK(c, hipStreamSynchronize(s.stream));
         s.inflight = false;
     }
+    c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
     const int r = stage_slot(c, s, z, nz, with_msa, full_caps);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(s.stream));
@@ -824,7 +844,10 @@ int ccsx_gpu_launch(ccsx_ctx *c, int mode, float *kernel_ms)
 int ccsx_gpu_fetch(ccsx_ctx *c, ccsx_zmw_out *out)
 {
     if (!c) return -1;
-    return fetch_slot(c, c->slot[0], out);
+    c->last_qual = 0;
+    const int r = fetch_slot(c, c->slot[0], out);
+    if (r == 0 || r == -2) c->last_qual = 2;
+    return r;
 }
 
 // The bytes one slot's slice may take: what is free plus what the workspaces
@@ -911,6 +934,10 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     using ms = std::chrono::duration<double, std::milli>;
     const auto t_run = std::chrono::steady_clock::now();
     c->run_arena.clear();
+    c->last_qual = 0;
+    c->run_qual.clear();
+    c->run_qoff.assign(c->quality ? nz : 0, 0);
+    c->run_qlen.assign(c->quality ? nz : 0, 0);
     c->run_bp.clear();
     c->run_bp_off.assign(nz, 0);
     c->run_bp_n.assign(nz, 0);
@@ -945,6 +972,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             size_t add = 0;
             for (size_t i = 0; i < s.nz; ++i) add += o[i].status ? 0 : o[i].len;
             c->run_arena.reserve(c->run_arena.size() + add);
+            if (s.qual) c->run_qual.reserve(c->run_qual.size() + add);
         }
         for (size_t i = 0; i < s.nz; ++i) {
             const uint32_t g = (*p.idx)[p.b + i];
@@ -965,6 +993,12 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             aoff[g] = c->run_arena.size();
             out[g].len = o[i].len;
             c->run_arena.insert(c->run_arena.end(), o[i].ccs, o[i].ccs + o[i].len);
+            if (s.qual) {
+                const uint8_t *q = s.h_out.p + s.out_bytes + s.desc[i].out_off;
+                c->run_qoff[g] = c->run_qual.size();
+                c->run_qlen[g] = o[i].len;
+                c->run_qual.insert(c->run_qual.end(), q, q + o[i].len);
+            }
             if (s.bp_words && mode == CCSX_MODE_SHRED) {
                 const uint32_t *lg = s.h_bp.data() + s.desc[i].bp_off;
                 c->run_bp_off[g] = c->run_bp.size() / 2;
@@ -1113,10 +1147,12 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     if (c->fault >= 0 && (size_t)c->fault < nz) {
         out[c->fault].status = ccsx::kErrTrace;
         out[c->fault].len = 0;
+        if (c->quality) c->run_qlen[c->fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     c->fault = -1;
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(c->run_arena.data() + aoff[i]);
+    if (c->quality) c->last_qual = 1;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1149,7 +1185,7 @@ int ccsx_gpu_reserve_staging(ccsx_ctx *c, uint64_t seq_bytes, uint64_t out_bytes
         if (c->tk[k].pending) continue;
         Slot &s = c->slot[k];
         HIPCHK(c, s.h_seq.reserve(seq_bytes, 0, true));
-        HIPCHK(c, s.h_out.reserve(out_bytes, 0, true));
+        HIPCHK(c, s.h_out.reserve(out_bytes * (c->quality ? 2 : 1), 0, true));  // (the quality plane too)
         break;
     }
     return 0;
@@ -1193,6 +1229,7 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
         c->err = m;
         return -4;
     }
+    if (si == 0 && c->last_qual == 2) c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
     r = stage_slot(c, s, z, nz, 0, 0);
     if (!r) r = launch_slot(c, s, mode);
     c->shred_caps = false;
@@ -1203,6 +1240,8 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     c->tk[si].z = z;
     c->tk[si].nz = nz;
     c->tk[si].fault = c->fault;
+    c->tk[si].qual = s.qual;
+    c->tk[si].has_qual = false;
     c->fault = -1;
     *slot = si;
     return 0;
@@ -1227,10 +1266,23 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
     std::vector<uint32_t> retry;
     std::string first_err;
     t.arena.clear();
+    t.has_qual = false;
+    t.qarena.clear();
+    t.qoff.assign(t.qual ? nz : 0, 0);
+    t.qlen.assign(t.qual ? nz : 0, 0);
+    // the full-cap re-run below stages as the batch was submitted, whatever
+    // ccsx_gpu_set_quality said since
+    struct Quality {
+        ccsx_ctx *c;
+        bool was;
+        Quality(ccsx_ctx *x, bool on) : c(x), was(x->quality) { c->quality = on; }
+        ~Quality() { c->quality = was; }
+    } quality(c, t.qual);
     auto gather = [&](const ccsx_zmw_out *res, const uint32_t *idx, size_t n, bool can_retry) {
         size_t add = 0;
         for (size_t i = 0; i < n; ++i) add += res[i].status ? 0 : res[i].len;
         t.arena.reserve(t.arena.size() + add);
+        if (s.qual) t.qarena.reserve(t.qarena.size() + add);
         for (size_t i = 0; i < n; ++i) {
             const uint32_t g = idx ? idx[i] : (uint32_t)i;
             out[g].cells = res[i].cells;
@@ -1250,6 +1302,13 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
             aoff[g] = t.arena.size();
             out[g].len = res[i].len;
             t.arena.insert(t.arena.end(), res[i].ccs, res[i].ccs + res[i].len);
+            if (s.qual) {
+                // (res[i].ccs points into the slot's CCS plane; the quality plane lies out_bytes behind)
+                const uint8_t *q = reinterpret_cast<const uint8_t *>(res[i].ccs) + s.out_bytes;
+                t.qoff[g] = t.qarena.size();
+                t.qlen[g] = res[i].len;
+                t.qarena.insert(t.qarena.end(), q, q + res[i].len);
+            }
         }
     };
     gather(o.data(), nullptr, nz, true);
@@ -1292,9 +1351,11 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
     if (t.fault >= 0 && (size_t)t.fault < nz) {
         out[t.fault].status = ccsx::kErrTrace;
         out[t.fault].len = 0;
+        if (t.qual) t.qlen[t.fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(t.arena.data() + aoff[i]);
+    t.has_qual = t.qual;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1419,6 +1480,61 @@ int ccsx_gpu_bp_log(const ccsx_ctx *c, size_t zmw, const uint32_t **pairs, uint3
     return 0;
 }
 
+int ccsx_gpu_set_quality(ccsx_ctx *c, int on)
+{
+    if (!c) return -1;
+    c->quality = on != 0;
+    return 0;
+}
+
+int ccsx_gpu_quality(ccsx_ctx *c, int slot, size_t zmw, const uint8_t **qual, uint32_t *len)
+{
+    if (!c || !qual || !len) return -1;
+    *qual = nullptr;
+    *len = 0;
+    if (slot < -1 || slot > 1) {
+        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
+        return -1;
+    }
+    const char *off = "that batch ran with quality off (ccsx_gpu_set_quality)";
+    const char *range = "ZMW index beyond the batch";
+    if (slot >= 0) {
+        const auto &t = c->tk[slot];
+        if (t.pending || !t.has_qual) {
+            c->err = t.pending ? "that slot's batch is not collected yet" : off;
+            return -1;
+        }
+        if (zmw >= t.qlen.size()) {
+            c->err = range;
+            return -1;
+        }
+        *qual = t.qarena.data() + t.qoff[zmw];
+        *len = t.qlen[zmw];
+        return 0;
+    }
+    if (c->last_qual == 1) {
+        if (zmw >= c->run_qlen.size()) {
+            c->err = range;
+            return -1;
+        }
+        *qual = c->run_qual.data() + c->run_qoff[zmw];
+        *len = c->run_qlen[zmw];
+        return 0;
+    }
+    const Slot &s = c->slot[0];
+    if (c->last_qual != 2 || !s.qual) {
+        c->err = off;
+        return -1;
+    }
+    if (zmw >= s.nz) {
+        c->err = range;
+        return -1;
+    }
+    *qual = s.h_out.p + s.out_bytes + s.desc[zmw].out_off;
+    *len = s.h_status[zmw] ? 0 : s.h_olen[zmw];
+    return 0;
+}
+
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -1469,7 +1585,7 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + s.msa_bytes;
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.msa_bytes;
 }
 
 // single-POA path used by the bspoa-compatible API (bspoa_gpu.cpp)

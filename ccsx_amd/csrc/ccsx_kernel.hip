@@ -501,7 +501,6 @@ __device__ __forceinline__ uint32_t rmeta_word(uint32_t off, uint32_t info, uint
     const bool two = !far && (info >> 8) <= 2u;
     return off | (far ? 0x80000000u : 0u) | (two ? 0x40000000u | ((dpk & 15u) << 22) | (((dpk >> 8) & 15u) << 26) : 0u);
 }
-constexpr uint32_t kMetaOff = 0x3FFFFFu;
 
 // the DP's row records {info, tag bytes} (written by merge): coalesced, no
 // dependent loads
@@ -3051,9 +3050,25 @@ __device__ __forceinline__ uint32_t find_breakpoint(const Z &z, uint32_t ncols, 
     return 0;
 }
 
-// emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag
-__device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, uint32_t &ol)
+// SPEC.md §9: the quality byte of column c, whose consensus is a base: the
+// reads on the consensus row (cmask) against the reads spanning the column
+__device__ __forceinline__ uint8_t column_qual(const Z &z, uint32_t c, uint32_t n)
 {
+    const uint32_t nw = z.d.nw;
+    const uint64_t *cmask = P<uint64_t>(z, z.L.cmask);
+    const uint32_t *rfc = P<uint32_t>(z, z.L.rfc), *rlc = P<uint32_t>(z, z.L.rlc);
+    uint32_t match = 0, cov = 0;
+    for (uint32_t w = 0; w < nw; ++w) match += (uint32_t)__builtin_popcountll(cmask[(size_t)c * nw + w]);
+    for (uint32_t k = 0; k < n; ++k) cov += (rfc[k] <= c && c <= rlc[k]) ? 1u : 0u;
+    return qual_phred(match, cov);
+}
+
+// emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag.
+// qual (KArgs::qual, may be null): the quality byte of every base written
+__device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
+                                     uint32_t &ol)
+{
+    uint8_t *qual = a.qual ? a.qual + z.d.out_off : nullptr;
     const uint32_t lane = lane_id(), nw = z.d.nw;
     const uint8_t *cons = P<uint8_t>(z, z.L.cons);
     if (flag) {
@@ -3079,6 +3094,7 @@ __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t 
         if (cb < 4) {
             const uint32_t o = ol + lanes_below(bal);
             if (o < z.d.outcap) out[o] = (uint8_t)"ACGT"[cb];
+            if (qual && o < z.d.outcap) qual[o] = column_qual(z, c, n);
         }
         ol += (uint32_t)__builtin_popcountll(bal);
     }
@@ -3177,7 +3193,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit(z, ncols, ncols, n, false, out, ol);
+            emit(z, ncols, ncols, n, false, out, a, ol);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3227,7 +3243,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit(z, i, ncols, n, flag, out, ol);
+            emit(z, i, ncols, n, flag, out, a, ol);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {

@@ -39,6 +39,8 @@ constexpr int kNeg = -(1 << 29);
 constexpr uint32_t kWinChunk = 8192;
 constexpr uint32_t kRdWinBytes = kWinChunk / 2;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
+// band offset bits of a row meta word (ZLayout::rmeta)
+constexpr uint32_t kMetaOff = 0x3FFFFFu;
 
 // The kernel configurations (ccsx_kernel.hip is compiled once per
 // configuration, ccsx_gpu.cpp picks one per slice):
@@ -113,6 +115,17 @@ struct ZLayout {
 
 CCSX_HD inline uint64_t align256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 
+// Per-base consensus quality (SPEC.md §9): a column whose consensus base is
+// carried by `match` of the `cov` reads spanning it scores kQStep per net vote
+// (agreeing reads minus spanning reads that disagree or have a gap), clamped
+// to [kQMin, kQMax].  Integer only: the device and the host compute the same byte.
+constexpr int32_t kQStep = 3, kQMin = 2, kQMax = 93;
+CCSX_HD inline uint8_t qual_phred(uint32_t match, uint32_t cov)
+{
+    const int64_t q = int64_t(kQStep) * (2 * int64_t(match) - int64_t(cov));
+    return uint8_t(q < kQMin ? kQMin : q > kQMax ? kQMax : q);
+}
+
 // The extension regions, in order (offsets relative to ZLayout::ext):
 //  * the far rows' slot records (rows with more than four predecessors or one
 //    beyond the DP ring, whose 8-bit cell records carry no tags): per cell the
@@ -155,7 +168,9 @@ CCSX_HD inline void zlayout(ZLayout &L, const ZmwDesc &d)
     L.mem1 = take(uint64_t(d.rcap) * d.nw * 8);
     L.poff1 = take(uint64_t(d.rcap + 1) * 4);
     L.pred1 = take(uint64_t(d.ecap) * 4);
-    L.rmeta = take(uint64_t(d.rcap) * 4);              // per DP row: band offset | far flag << 31
+    // per DP row (ccsx_kernel.hip rmeta_word): band offset (bits 0-21, kMetaOff) | for a row of one or
+    // two predecessors the distances - 1 of slots 0 / 1 (bits 22-25 / 26-29) and bit 30 | far flag << 31
+    L.rmeta = take(uint64_t(d.rcap) * 4);
     L.spf = take(d.rcap);                              // per row: needed beyond the LDS ring
     L.sslot = take(uint64_t(d.rcap) * 4);              // per spilled row: its spill record
     L.codes = take(uint64_t(d.rcap) * kRecRow);        // cell records, 8 bits/cell, 128 B/row
@@ -253,6 +268,7 @@ struct KArgs {
     uint32_t lds_nmax;
     unsigned long long *prof;  // optional: kProfSlots shader-clock counters per ZMW (diagnostics)
     uint32_t *bplog;           // optional: per-round breakpoint log (main.c:619-620, ZmwDesc::bp_off)
+    uint8_t *qual;             // optional: a quality byte (0..kQMax, not ASCII) per CCS byte, same offsets as out
 };
 
 // phase counters written when KArgs::prof != nullptr

@@ -120,6 +120,8 @@ struct Zmw {
     std::vector<uint32_t> seg_off, seg_len;
     std::vector<uint8_t> seg_rev;
     std::string ccs;
+    std::string qual;         // -q: the CCS bases' qualities, Q + 33
+    double rq = 0;            // -q: predicted accuracy of the read (ccsx_qual_rq)
     int32_t status = 0;
     std::vector<uint32_t> bp;  // -v >= 3: (breakpoint, MSA columns) per shredding round
 };
@@ -162,6 +164,7 @@ int usage()
             "-c     <int>   Minimum number of subreads required to generate CCS. [3] \n"
             "-A             For fasta/fastq input,gzip allowed  \n"
             "-P             primitive bsalign,subread shred by default \n"
+            "-q             Output fastq: per-base consensus qualities (Q+33), np= and rq= in the header \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
             "\n"
@@ -455,16 +458,17 @@ int main(int argc, char **argv)
         mallopt(M_TRIM_THRESHOLD, 1 << 30);
     }
     int c, verbose = 0, min_subread_len = 5000, max_subread_len = 500000, min_fulllen_count = 3, nthreads = 1;
-    int isbam = 1, split_subread = 1;
+    int isbam = 1, split_subread = 1, fastq = 0;
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAv")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvq")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
         case 'P': split_subread = 0; break;
         case 'A': isbam = 0; break;
+        case 'q': fastq = 1; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -606,6 +610,7 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
+        bool qfail = false;  // -q: the batch's qualities are missing (a context error)
         if (r == 0 || r == -2) {
             // -2: some ZMWs failed on the device, the rest are valid
             uint64_t cells = 0;
@@ -615,12 +620,25 @@ int main(int argc, char **argv)
                 Zmw &z = ch.zs[f.b.idx[i]];
                 z.status = f.out[i].status;
                 if (!f.out[i].status) z.ccs.assign(f.out[i].ccs, f.out[i].len);
+                if (fastq && !f.out[i].status) {
+                    // (f.slot: the collected slot, -1 for a batch ccsx_gpu_run ran)
+                    const uint8_t *q = nullptr;
+                    uint32_t ql = 0;
+                    if (ccsx_gpu_quality(ctx[w], f.slot, i, &q, &ql) != 0 || ql != f.out[i].len) {
+                        qfail = true;
+                        break;
+                    }
+                    z.rq = ccsx_qual_rq(q, ql);
+                    z.qual.resize(ql);
+                    for (uint32_t k = 0; k < ql; ++k) z.qual[k] = (char)(q[k] + 33);
+                }
                 const uint32_t *lg;
                 uint32_t nr = 0;
                 if (verbose > 2 && !f.out[i].status && ccsx_gpu_bp_log(ctx[w], i, &lg, &nr) == 0)
                     z.bp.assign(lg, lg + 2 * (size_t)nr);
             }
-        } else if (!fatal.exchange(true)) {
+        }
+        if ((qfail || (r != 0 && r != -2)) && !fatal.exchange(true)) {
             std::lock_guard<std::mutex> g(err_m);
             fprintf(stderr, "[ccsx] device context %d: %s\n", w, r == -9 ? "injected fatal error (test hook)" : ccsx_gpu_error(ctx[w]));
         }
@@ -807,6 +825,7 @@ int main(int argc, char **argv)
             ccsx_gpu_set_mem_share(ctx[i], (uint32_t)(per_dev[dev] * dev_share));
             ccsx_gpu_set_prealloc(ctx[i], 1);
             if (verbose > 2 && split_subread) ccsx_gpu_set_bp_log(ctx[i], 1);
+            if (fastq) ccsx_gpu_set_quality(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
@@ -862,7 +881,11 @@ int main(int argc, char **argv)
                         continue;
                     }
                     if (verbose > 1) fprintf(stderr, "poa end %s\n", z.hole.c_str());
-                    if (!z.ccs.empty())
+                    if (z.ccs.empty()) continue;
+                    if (fastq)
+                        fprintf(fp_out, "@%s/%s/ccs np=%zu rq=%.6f\n%s\n+\n%s\n", z.movie.c_str(), z.hole.c_str(),
+                                z.seg_len.size(), z.rq, z.ccs.c_str(), z.qual.c_str());
+                    else
                         fprintf(fp_out, ">%s/%s/ccs\n%s\n", z.movie.c_str(), z.hole.c_str(), z.ccs.c_str());
                 }
             }

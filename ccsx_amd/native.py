@@ -29,10 +29,11 @@ EXPORTS = {
                    "ccsx_gpu_set_bp_log", "ccsx_gpu_bp_log", "ccsx_gpu_stage_for",
                    "ccsx_gpu_run_stats", "ccsx_gpu_zmw_bytes", "ccsx_gpu_set_slot_budget", "ccsx_gpu_set_wg_cap",
                    "ccsx_gpu_set_shred_read_cap", "ccsx_gpu_set_mem_frac", "ccsx_gpu_set_mem_wait",
-                   "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging"],
+                   "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
+                   "ccsx_gpu_set_quality", "ccsx_gpu_quality"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
-                    "ccsx_zmw_cost", "ccsx_partition",
+                    "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq",
                     "ccsx_synth_batch_make", "ccsx_synth_batch_zmws", "ccsx_synth_batch_free"],
     "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_close"],
 }
@@ -102,6 +103,14 @@ def lib() -> C.CDLL:
         L.ccsx_gpu_set_bp_log.argtypes = [C.c_void_p, C.c_int]
         L.ccsx_gpu_bp_log.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint32)),
                                       C.POINTER(C.c_uint32)]
+        if hasattr(L, "ccsx_gpu_set_quality"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_gpu_set_quality.argtypes = [C.c_void_p, C.c_int]
+            L.ccsx_gpu_quality.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_uint32)]
+            L.ccsx_qual_phred.argtypes = [C.c_uint32, C.c_uint32]
+            L.ccsx_qual_phred.restype = C.c_uint8
+            L.ccsx_qual_rq.argtypes = [C.c_void_p, C.c_uint32]
+            L.ccsx_qual_rq.restype = C.c_double
         L.ccsx_revcomp.argtypes = [C.c_char_p, C.c_uint32]
         L.ccsx_prepare.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
@@ -215,6 +224,20 @@ def partition(costs, nparts: int, min_batch: int):
 def pairwise(q: bytes, t: bytes) -> dict:
     r = lib().ccsx_pairwise(q, len(q), t, len(t))
     return {n if n != "del_" else "del": getattr(r, n) for n, _ in PairAln._fields_}
+
+
+def qual_phred(match: int, cov: int) -> int:
+    """ccsx_qual_phred: the quality of a column whose consensus base `match`
+    of the `cov` reads spanning it carry (SPEC.md §9)."""
+    return int(lib().ccsx_qual_phred(match, cov))
+
+
+def qual_rq(qual) -> float:
+    """ccsx_qual_rq: predicted accuracy 1 - mean(10^(-Q/10)) of a read's raw
+    quality bytes (0.0 for none)."""
+    q = np.ascontiguousarray(np.frombuffer(qual, dtype=np.uint8) if isinstance(qual, (bytes, bytearray)) else
+                             np.asarray(qual, dtype=np.uint8))
+    return float(lib().ccsx_qual_rq(q.ctypes.data, len(q)))
 
 
 def read_calls(path: str, is_bam: bool = False):
@@ -448,6 +471,22 @@ class Engine:
             self._err("ccsx_gpu_collect")
         return [(C.string_at(out[i].ccs, out[i].len) if out[i].len else b"", out[i].status, out[i].cells)
                 for i in range(n)]
+
+    def set_quality(self, on: bool = True) -> None:
+        """Per-base qualities for the following stage / run / submit calls
+        (ccsx_gpu_set_quality): a second output plane, read with quality()."""
+        if self._L.ccsx_gpu_set_quality(self._ctx, 1 if on else 0) != 0:
+            self._err("ccsx_gpu_set_quality")
+
+    def quality(self, i: int, slot: int = -1) -> bytes:
+        """Raw quality bytes (0..93) of ZMW i: of the last run() / fetch()
+        (slot -1) or of the batch collected from `slot`; raises if that batch
+        ran with quality off."""
+        p = C.c_void_p()
+        n = C.c_uint32(0)
+        if self._L.ccsx_gpu_quality(self._ctx, slot, i, C.byref(p), C.byref(n)) != 0:
+            self._err("ccsx_gpu_quality")
+        return C.string_at(p, n.value) if n.value else b""
 
     def set_bp_log(self, on: bool = True) -> None:
         """Record the -v >= 3 breakpoint log (main.c:619-620) in ccsx_gpu_run."""

@@ -80,7 +80,8 @@ int ccsx_gpu_run(ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_
  * once the submitted batches are collected (ccsx_gpu_run drops uncollected
  * ones).  collect returns 0, -2 (some ZMWs failed) or -1. */
 int ccsx_gpu_slot_bytes(ccsx_ctx *ctx, uint64_t *bytes);
-/* Reserve the pinned host staging (subreads, CCS; exactly these sizes) of
+/* Reserve the pinned host staging (subreads, CCS; exactly these sizes, the
+ * CCS size twice with ccsx_gpu_set_quality on) of
  * the slot the next submit takes, e.g. on a worker thread while the first
  * batch is still being read, instead of in that batch's staging (huge-page
  * mapping, touch, registration: ~0.1 s per GB).  The other slot's is sized by
@@ -110,6 +111,27 @@ int ccsx_gpu_set_prealloc(ccsx_ctx *ctx, int on);
  * batch) as nrounds (i, ncols) pairs, ctx-owned until the next run. */
 int ccsx_gpu_set_bp_log(ccsx_ctx *ctx, int on);
 int ccsx_gpu_bp_log(const ccsx_ctx *ctx, size_t zmw, const uint32_t **pairs, uint32_t *nrounds);
+/* Per-base consensus qualities (SPEC.md section 9), off by default.  on != 0:
+ * the following ccsx_gpu_stage* / ccsx_gpu_run / ccsx_gpu_submit calls give
+ * every ZMW a second output plane, device and pinned host, of one quality byte
+ * (0 .. 93, not ASCII) per CCS byte, written by the kernel's emission and
+ * copied back with the CCS.  With quality on, ccsx_gpu_zmw_bytes, the batch
+ * size ccsx_gpu_submit checks against ccsx_gpu_slot_bytes,
+ * ccsx_gpu_staged_bytes and the output size ccsx_gpu_reserve_staging pins
+ * include that plane (the ZMW's output slab once more); with quality off they,
+ * the kernel's work and the bytes copied are what they are without this call.
+ * A batch keeps the setting it was staged or submitted with (the full-capacity
+ * re-run inside ccsx_gpu_collect included).  The bspoa-compatible single-POA
+ * mode (ccsx_bspoa.h) has no qualities.
+ * ccsx_gpu_quality: the qualities of ZMW `zmw` of a batch, *len bytes (= that
+ * ZMW's out[i].len; 0 for a ZMW without CCS): slot -1 = the last ccsx_gpu_run
+ * or ccsx_gpu_fetch on this context, 0 / 1 = that slot's last collected
+ * ccsx_gpu_submit batch.  ctx-owned, valid as long as that batch's out[i].ccs.
+ * Returns -1 (ccsx_gpu_error says why) if the batch ran with quality off, is
+ * not collected yet, or has no ZMW `zmw`.  The read-level values derived from
+ * them are ccsx_qual_rq (ccsx_host.h) and np = the ZMW's nseg. */
+int ccsx_gpu_set_quality(ccsx_ctx *ctx, int on);
+int ccsx_gpu_quality(ccsx_ctx *ctx, int slot, size_t zmw, const uint8_t **qual, uint32_t *len);
 /* The same in three steps (one slice, tight capacities, no re-run), so inputs
  * can stay resident in HBM across launches (used by bench.py).
  * ccsx_gpu_launch returns the kernel time measured with HIP events on the
@@ -123,7 +145,8 @@ int ccsx_gpu_stage_for(ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z, size_t nz)
 int ccsx_gpu_launch(ccsx_ctx *ctx, int mode, float *kernel_ms);
 int ccsx_gpu_fetch(ccsx_ctx *ctx, ccsx_zmw_out *out);
 
-/* Device bytes the staged batch occupies (workspace + arenas). */
+/* Device bytes the staged batch occupies (workspace + arenas; the quality
+ * plane when the batch has one). */
 uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *ctx);
 
 /* Diagnostics: per-phase shader-clock counters (s_memtime) summed over the
@@ -152,7 +175,7 @@ int ccsx_gpu_set_stage_piece(ccsx_ctx *ctx, uint64_t bytes);
  * latency configuration 0 -- three waves, 8-row DP blocks, 32-row LDS ring --
  * when it keeps the whole slice resident; for slices of at least 3x what the
  * occupancy one keeps resident a one-wave-per-ZMW configuration with an int16
- * ring: 5 (solo16w, 24 per CU) when the slice's ZMWs average fewer than 16
+ * ring: 5 (solo16w, 24 per CU) when the slice's ZMWs average fewer than 64
  * segments, else 4 (solo16, 20 per CU), or 3 (solo, int32 ring) where a
  * pushed read exceeds 16,256 bases or the slice runs the HBM-read instance;
  * else the occupancy configuration 1 -- 4-row blocks, 24-row ring); 0 .. 5
@@ -175,7 +198,8 @@ int ccsx_gpu_run_stats(const ccsx_ctx *ctx, uint64_t *stats, uint32_t n);
  * not even one ZMW fits; a ccsx_gpu_submit batch waits for its whole size. */
 int ccsx_gpu_set_mem_wait(ccsx_ctx *ctx, uint32_t ms);
 /* Device bytes ZMW *z occupies in a ccsx_gpu_run slice of `mode` (tight
- * capacities: workspace, subreads, output slab, tables). */
+ * capacities: workspace, subreads, output slab -- twice with quality on --,
+ * tables). */
 uint64_t ccsx_gpu_zmw_bytes(const ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z);
 /* Test hook: bytes per slot for ccsx_gpu_run's slices (0 = by device memory:
  * half of this context's share, ccsx_gpu_set_mem_share), so a small batch is

@@ -53,6 +53,14 @@ uint64_t ccsx_zmw_cost(const uint32_t *seg_len, uint32_t nseg);
 uint32_t ccsx_partition(const uint64_t *cost, uint32_t n, uint32_t nparts, uint32_t min_batch,
                         uint32_t *order, uint32_t *bounds);
 
+/* Per-base consensus quality (SPEC.md section 9), the formula the kernel
+ * applies per emitted column: clamp(3 x (2 x match - cov), 2, 93) for a column
+ * whose consensus base `match` of the `cov` reads spanning it carry.
+ * ccsx_qual_rq: the predicted read accuracy 1 - mean(10^(-Q/10)) over a
+ * read's quality bytes (raw, not ASCII), in double; 0.0 for len == 0. */
+uint8_t ccsx_qual_phred(uint32_t match, uint32_t cov);
+double ccsx_qual_rq(const uint8_t *qual, uint32_t len);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
