@@ -173,6 +173,29 @@ struct DevBuf {
 };
 
 
+// The gathered pass records (SPEC.md §10) of one ccsx_gpu_run call or one
+// collected batch, per ZMW of the call in input order
+struct PassSet {
+    std::vector<uint32_t> words;   // kPassWords per segment
+    std::vector<uint64_t> off;     // per ZMW: word offset into words
+    std::vector<uint32_t> nseg;    // per ZMW: records
+    std::vector<uint8_t> ok;       // per ZMW: it has a result (status 0)
+    void reset(size_t nz)
+    {
+        words.clear();
+        off.assign(nz, 0);
+        nseg.assign(nz, 0);
+        ok.assign(nz, 0);
+    }
+    void put(size_t g, const uint32_t *rec, uint32_t n)
+    {
+        off[g] = words.size();
+        nseg[g] = n;
+        ok[g] = 1;
+        words.insert(words.end(), rec, rec + size_t(n) * ccsx::kPassWords);
+    }
+};
+
 // One staged slice and everything it owns on the device and the host.  A
 // context has two: ccsx_gpu_run stages and launches slice k + 1 on the other
 // slot's stream while slice k's kernel runs, so one slice's tail (the launch
@@ -191,10 +214,19 @@ struct Slot {
     // staged with a quality plane (ccsx_gpu_set_quality): out_bytes more behind
     // the CCS plane in d_out and h_out, a byte per CCS byte at the same offsets
     bool qual = false;
+    // staged with pass records (ccsx_gpu_set_pass_stats): kPassWords words per
+    // segment in d_pstat; in h_out at pst_off(), behind the plane(s)
+    bool pstat = false;
+    uint64_t pst_off() const { return (out_bytes * (qual ? 2 : 1) + 7) & ~uint64_t(7); }
+    uint64_t pst_bytes() const { return pstat ? uint64_t(nseg_total) * ccsx::kPassWords * 4 : 0; }
+    const uint32_t *h_pstat(size_t zmw) const
+    {
+        return reinterpret_cast<const uint32_t *>(h_out.p + pst_off()) + size_t(desc[zmw].seg0) * ccsx::kPassWords;
+    }
     std::vector<ccsx::ZmwDesc> desc;
     std::vector<uint32_t> hoff, hlen, order;  // host copies the async H2D reads from
     DevBuf d_prof, d_bp;
-    DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells;
+    DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells, d_pstat;
     HostBuf h_out, h_seq;
     std::vector<uint32_t> h_olen, h_ncols, h_bp;
     std::vector<int32_t> h_status;
@@ -203,7 +235,7 @@ struct Slot {
     void release()
     {
         DevBuf *bufs[] = {&d_bp, &d_prof, &d_seq, &d_soff, &d_slen, &d_desc, &d_order, &d_ws, &d_out,
-                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells};
+                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_pstat};
         for (DevBuf *b : bufs) b->release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -257,6 +289,10 @@ struct ccsx_ctx {
     std::vector<uint8_t> run_qual;     // ccsx_gpu_run's gathered qualities (run_arena's offsets)
     std::vector<uint64_t> run_qoff;    // per ZMW of the call: offset into run_qual
     std::vector<uint32_t> run_qlen;    // per ZMW of the call: quality bytes (0: no CCS)
+    bool pass_stats = false;           // stage pass records beside the CCS (ccsx_gpu_set_pass_stats)
+    // ccsx_gpu_pass_stats(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
+    int last_pst = 0;
+    PassSet run_pst;                   // ccsx_gpu_run's gathered pass records
     std::vector<uint32_t> run_bp;      // ccsx_gpu_run: the gathered logs, (i, ncols) pairs
     std::vector<uint64_t> run_bp_off;  // per ZMW of the call: offset into run_bp (pairs)
     std::vector<uint32_t> run_bp_n;    // per ZMW of the call: rounds
@@ -274,6 +310,9 @@ struct ccsx_ctx {
         std::vector<uint8_t> qarena;   // the collected batch's qualities (arena's offsets)
         std::vector<uint64_t> qoff;
         std::vector<uint32_t> qlen;
+        bool pstat = false;            // submitted with pass statistics on
+        bool has_pst = false;          // collected, and pst holds its pass records
+        PassSet pst;
     } tk[2];
 };
 
@@ -425,7 +464,7 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::ZLayout L;
     ccsx::zlayout(L, d);
     return ccsx::align256(L.total) + hi + d.outcap + (c->quality ? d.outcap : 0u) + uint64_t(zi.nseg) * 8 +
-           sizeof(ccsx::ZmwDesc) + 32;
+           (c->pass_stats ? uint64_t(zi.nseg) * ccsx::kPassWords * 4 : 0u) + sizeof(ccsx::ZmwDesc) + 32;
 }
 
 // The bytes a slice staged into slot s may need now: the device's free memory
@@ -438,7 +477,7 @@ static int slot_avail(ccsx_ctx *c, const Slot &s, uint64_t &avail)
 {
     size_t freeb = 0, totb = 0;
     HIPCHK(c, hipMemGetInfo(&freeb, &totb));
-    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap;
+    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap + s.d_pstat.cap;
     avail = have > (1ull << 30) ? have - (1ull << 30) : 0;
     return 0;
 }
@@ -518,6 +557,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     s.nseg_total = nseg;
     s.qual = c->quality && !with_msa;
     const uint64_t qual_b = s.qual ? out_b : 0;
+    s.pstat = c->pass_stats && !with_msa;
+    const uint64_t pst_b = s.pst_bytes();
     // 2-bit read buffer (ccsx_kernel.hip stage_read); at least one band:
     // every lane reads its window bytes even when the read is shorter.  A
     // slice with a read or a cursor array beyond the LDS budget runs the
@@ -573,7 +614,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + qual_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
+    const uint64_t need = seq_b + ws_b + out_b + qual_b + pst_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
         // already cut the slice to what is free; a submitted batch cannot be cut)
@@ -600,6 +641,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, s.d_order.reserve(nz * 4));
     HIPCHK(c, s.d_ws.reserve(ws_b));
     HIPCHK(c, s.d_out.reserve(out_b + qual_b));
+    if (pst_b) HIPCHK(c, s.d_pstat.reserve(pst_b));
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
     HIPCHK(c, s.d_ncols.reserve(nz * 4));
@@ -725,6 +767,7 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     a.prof = nullptr;
     a.bplog = s.bp_words ? s.d_bp.as<uint32_t>() : nullptr;
     a.qual = s.qual ? s.d_out.as<uint8_t>() + s.out_bytes : nullptr;
+    a.pstat = s.pst_bytes() ? s.d_pstat.as<uint32_t>() : nullptr;
     if (c->profiling) {
         HIPCHK(c, s.d_prof.reserve(s.nz * ccsx::kProfSlots * 8));
         a.prof = s.d_prof.as<unsigned long long>();
@@ -749,7 +792,9 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nz = s.nz;
     const uint64_t planes = s.qual ? 2 : 1;  // the quality plane follows the CCS plane, one copy for both
-    HIPCHK(c, s.h_out.reserve(s.out_bytes * planes, c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
+    // (the pass records follow the planes, 8-byte aligned)
+    HIPCHK(c, s.h_out.reserve(s.pstat ? s.pst_off() + s.pst_bytes() : s.out_bytes * planes,
+                              c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
     s.h_olen.resize(nz);
     s.h_status.resize(nz);
     s.h_cells.resize(nz);
@@ -759,6 +804,8 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
         HIPCHK(c, hipMemcpyAsync(s.h_status.data(), s.d_status.p, nz * 4, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipMemcpyAsync(s.h_cells.data(), s.d_cells.p, nz * 8, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes * planes, hipMemcpyDeviceToHost, s.stream));
+        if (s.pst_bytes())
+            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pst_off(), s.d_pstat.p, s.pst_bytes(), hipMemcpyDeviceToHost, s.stream));
         if (s.bp_words)
             HIPCHK(c, hipMemcpyAsync(s.h_bp.data(), s.d_bp.p, s.bp_words * 4, hipMemcpyDeviceToHost, s.stream));
     }
@@ -794,6 +841,7 @@ int ccsx_gpu_stage_ex(ccsx_ctx *c, const ccsx_zmw_in *z, size_t nz, int with_msa
         s.inflight = false;
     }
     c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
+    c->last_pst = 0;
     const int r = stage_slot(c, s, z, nz, with_msa, full_caps);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(s.stream));
@@ -845,8 +893,9 @@ int ccsx_gpu_fetch(ccsx_ctx *c, ccsx_zmw_out *out)
 {
     if (!c) return -1;
     c->last_qual = 0;
+    c->last_pst = 0;
     const int r = fetch_slot(c, c->slot[0], out);
-    if (r == 0 || r == -2) c->last_qual = 2;
+    if (r == 0 || r == -2) c->last_qual = c->last_pst = 2;
     return r;
 }
 
@@ -938,6 +987,8 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     c->run_qual.clear();
     c->run_qoff.assign(c->quality ? nz : 0, 0);
     c->run_qlen.assign(c->quality ? nz : 0, 0);
+    c->last_pst = 0;
+    c->run_pst.reset(c->pass_stats ? nz : 0);
     c->run_bp.clear();
     c->run_bp_off.assign(nz, 0);
     c->run_bp_n.assign(nz, 0);
@@ -999,6 +1050,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
                 c->run_qlen[g] = o[i].len;
                 c->run_qual.insert(c->run_qual.end(), q, q + o[i].len);
             }
+            if (s.pstat) c->run_pst.put(g, s.h_pstat(i), s.desc[i].n);
             if (s.bp_words && mode == CCSX_MODE_SHRED) {
                 const uint32_t *lg = s.h_bp.data() + s.desc[i].bp_off;
                 c->run_bp_off[g] = c->run_bp.size() / 2;
@@ -1148,11 +1200,13 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
         out[c->fault].status = ccsx::kErrTrace;
         out[c->fault].len = 0;
         if (c->quality) c->run_qlen[c->fault] = 0;
+        if (c->pass_stats) c->run_pst.ok[c->fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     c->fault = -1;
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(c->run_arena.data() + aoff[i]);
     if (c->quality) c->last_qual = 1;
+    if (c->pass_stats) c->last_pst = 1;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1230,6 +1284,7 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
         return -4;
     }
     if (si == 0 && c->last_qual == 2) c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
+    if (si == 0 && c->last_pst == 2) c->last_pst = 0;
     r = stage_slot(c, s, z, nz, 0, 0);
     if (!r) r = launch_slot(c, s, mode);
     c->shred_caps = false;
@@ -1242,6 +1297,8 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     c->tk[si].fault = c->fault;
     c->tk[si].qual = s.qual;
     c->tk[si].has_qual = false;
+    c->tk[si].pstat = s.pstat;
+    c->tk[si].has_pst = false;
     c->fault = -1;
     *slot = si;
     return 0;
@@ -1278,6 +1335,14 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         Quality(ccsx_ctx *x, bool on) : c(x), was(x->quality) { c->quality = on; }
         ~Quality() { c->quality = was; }
     } quality(c, t.qual);
+    t.has_pst = false;
+    t.pst.reset(t.pstat ? nz : 0);
+    struct PassStats {
+        ccsx_ctx *c;
+        bool was;
+        PassStats(ccsx_ctx *x, bool on) : c(x), was(x->pass_stats) { c->pass_stats = on; }
+        ~PassStats() { c->pass_stats = was; }
+    } pass_stats(c, t.pstat);
     auto gather = [&](const ccsx_zmw_out *res, const uint32_t *idx, size_t n, bool can_retry) {
         size_t add = 0;
         for (size_t i = 0; i < n; ++i) add += res[i].status ? 0 : res[i].len;
@@ -1309,6 +1374,8 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
                 t.qlen[g] = res[i].len;
                 t.qarena.insert(t.qarena.end(), q, q + res[i].len);
             }
+            // (gather's results are the slot's, in its order: ZMW i of the slot)
+            if (s.pstat) t.pst.put(g, s.h_pstat(i), s.desc[i].n);
         }
     };
     gather(o.data(), nullptr, nz, true);
@@ -1352,10 +1419,12 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         out[t.fault].status = ccsx::kErrTrace;
         out[t.fault].len = 0;
         if (t.qual) t.qlen[t.fault] = 0;
+        if (t.pstat) t.pst.ok[t.fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(t.arena.data() + aoff[i]);
     t.has_qual = t.qual;
+    t.has_pst = t.pstat;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1535,6 +1604,68 @@ int ccsx_gpu_quality(ccsx_ctx *c, int slot, size_t zmw, const uint8_t **qual, ui
     return 0;
 }
 
+int ccsx_gpu_set_pass_stats(ccsx_ctx *c, int on)
+{
+    if (!c) return -1;
+    c->pass_stats = on != 0;
+    return 0;
+}
+
+int ccsx_gpu_pass_stats(ccsx_ctx *c, int slot, size_t zmw, const ccsx_pass_stat **st, uint32_t *nseg)
+{
+    static_assert(sizeof(ccsx_pass_stat) == ccsx::kPassWords * 4, "ccsx_pass_stat is the kernel's record");
+    if (!c || !st || !nseg) return -1;
+    *st = nullptr;
+    *nseg = 0;
+    if (slot < -1 || slot > 1) {
+        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
+        return -1;
+    }
+    const char *off = "that batch ran with pass statistics off (ccsx_gpu_set_pass_stats)";
+    const char *range = "ZMW index beyond the batch";
+    const char *failed = "that ZMW failed: it has no pass statistics";
+    const PassSet *ps = nullptr;
+    if (slot >= 0) {
+        const auto &t = c->tk[slot];
+        if (t.pending || !t.has_pst) {
+            c->err = t.pending ? "that slot's batch is not collected yet" : off;
+            return -1;
+        }
+        ps = &t.pst;
+    } else if (c->last_pst == 1) {
+        ps = &c->run_pst;
+    }
+    if (ps) {
+        if (zmw >= ps->nseg.size()) {
+            c->err = range;
+            return -1;
+        }
+        if (!ps->ok[zmw]) {
+            c->err = failed;
+            return -1;
+        }
+        *st = reinterpret_cast<const ccsx_pass_stat *>(ps->words.data() + ps->off[zmw]);
+        *nseg = ps->nseg[zmw];
+        return 0;
+    }
+    const Slot &s = c->slot[0];
+    if (c->last_pst != 2 || !s.pstat) {
+        c->err = off;
+        return -1;
+    }
+    if (zmw >= s.nz) {
+        c->err = range;
+        return -1;
+    }
+    if (s.h_status[zmw]) {
+        c->err = failed;
+        return -1;
+    }
+    *st = reinterpret_cast<const ccsx_pass_stat *>(s.h_pstat(zmw));
+    *nseg = s.desc[zmw].n;
+    return 0;
+}
+
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -1585,7 +1716,7 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.msa_bytes;
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.pst_bytes() + s.msa_bytes;
 }
 
 // single-POA path used by the bspoa-compatible API (bspoa_gpu.cpp)

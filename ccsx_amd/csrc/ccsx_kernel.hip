@@ -3063,11 +3063,120 @@ __device__ __forceinline__ uint8_t column_qual(const Z &z, uint32_t c, uint32_t 
     return qual_phred(match, cov);
 }
 
+// SPEC.md §10, one 64-column chunk of pass_stats (lane = column c): the
+// column's consensus code, rows [ra, re) and matching reads (mask word w).
+// Branch-free: a lane beyond the emitted columns loads column 0 and is masked,
+// so the loads of a later chunk can be in flight under the current one's work
+struct PsCols {
+    uint32_t cb, ra, re;
+    uint64_t m;
+};
+__device__ __forceinline__ PsCols ps_cols(const Z &z, uint32_t c, uint32_t i, uint32_t w)
+{
+    const bool v = c < i;
+    const uint32_t cc = v ? c : 0u;
+    const uint32_t *colrow = P<uint32_t>(z, z.L.colrow);
+    PsCols x;
+    x.cb = P<uint8_t>(z, z.L.cons)[cc];
+    x.ra = colrow[cc];
+    x.re = colrow[cc + 1];
+    x.m = P<uint64_t>(z, z.L.cmask)[(size_t)cc * z.d.nw + w];
+    if (!v) x.cb = 4u, x.re = x.ra, x.m = 0ull;
+    return x;
+}
+
+// the reads with a base in the column of rows [ra, re): the OR of the rows'
+// bitsets (a read has at most one base per column).  Four rows at once, loaded
+// unconditionally (most columns have one or two rows; row ra again where a
+// column has fewer), the rest in a loop only where some column of the chunk has more
+__device__ __forceinline__ uint64_t ps_rows(const uint64_t *mem, uint32_t ra, uint32_t re, uint32_t nw, uint32_t w)
+{
+    uint64_t x[4];
+#pragma unroll
+    for (uint32_t u = 0; u < 4; ++u) x[u] = mem[(size_t)(ra + u < re ? ra + u : ra) * nw + w];
+    uint64_t h = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < 4; ++u) h |= ra + u < re ? x[u] : 0ull;
+    if (ballot(ra + 4 < re))
+        for (uint32_t r = ra + 4; r < re; ++r) h |= mem[(size_t)r * nw + w];
+    return h;
+}
+
+// SPEC.md §10: add the emitted columns [0, i) of this POA call to the reads'
+// pass records ps (KArgs::pstat at the ZMW's first segment); ol = the CCS bases
+// emitted before this call.  Per 64 reads (mask word w, lane = read) the wave
+// walks the columns 64 at a time (lane = column): a column's reads are the OR
+// of its rows' bitsets, its matching reads are cmask; one ballot + popcount per
+// read bit counts them over the 64 columns, split by the ballot of the base
+// columns into match + mismatch and ins, and lane `bit` takes the three counts
+// packed in one word.  The same ballot's prefix counts give every read the CCS
+// offsets of its span's ends, hence cbeg / cend and del.  The loads run two
+// chunks ahead (columns) and one ahead (rows) of the ballots.
+__device__ __forceinline__ void pass_stats(const Z &z, uint32_t i, uint32_t n, uint32_t ol, uint32_t *ps)
+{
+    const uint32_t lane = lane_id(), nw = z.d.nw;
+    const uint64_t *mem = G_mem(z, z.cur);
+    const uint32_t *rfc = P<uint32_t>(z, z.L.rfc), *rlc = P<uint32_t>(z, z.L.rlc);
+    if (i == 0) return;
+    for (uint32_t w = 0; w * 64 < n; ++w) {
+        const uint32_t k = w * 64 + lane;
+        const uint32_t kn = n - w * 64 < 64 ? n - w * 64 : 64;
+        // the read's emitted span [f, e); e = 0: none (rfc = kNone for a read without bases)
+        const uint32_t f = k < n ? rfc[k] : kNone;
+        const uint32_t l1 = f < i ? rlc[k] + 1u : 0u;
+        const uint32_t e = l1 < i ? l1 : f < i ? i : 0u;
+        uint32_t hb = 0, mt = 0, ins = 0;  // read k: bases in base columns, of them matching, bases in gap columns
+        uint32_t bf = 0, be = 0, base = 0;  // base columns before f / before e / before c0
+        PsCols x0 = ps_cols(z, lane, i, w), x1 = ps_cols(z, 64 + lane, i, w);
+        uint64_t h = ps_rows(mem, x0.ra, x0.re, nw, w);
+        for (uint32_t c0 = 0; c0 < i; c0 += 64) {
+            const PsCols x2 = ps_cols(z, c0 + 128 + lane, i, w);
+            const uint64_t h1 = ps_rows(mem, x1.ra, x1.re, nw, w);
+            const uint64_t bm = ballot(x0.cb < 4);
+            // lane k0 + kb: the chunk's counts of read bit k0 + kb, a byte each (<= 64)
+            uint32_t pk = 0;
+            // (32 read bits at a time: the tests stay 32-bit)
+            for (uint32_t k0 = 0; k0 < kn; k0 += 32) {
+                const uint32_t hx = (uint32_t)(h >> k0), mx = (uint32_t)(x0.m >> k0);
+                const uint32_t cnt = kn - k0 < 32 ? kn - k0 : 32;
+                for (uint32_t kb = 0; kb < cnt; ++kb) {
+                    const uint64_t bh = ballot((hx & (1u << kb)) != 0), bq = ballot((mx & (1u << kb)) != 0);
+                    const uint32_t val = (uint32_t)__builtin_popcountll(bh & bm) | (uint32_t)__builtin_popcountll(bh & ~bm) << 8 |
+                                         (uint32_t)__builtin_popcountll(bq) << 16;
+                    pk = lane == k0 + kb ? val : pk;
+                }
+            }
+            hb += pk & 255u;
+            ins += (pk >> 8) & 255u;
+            mt += pk >> 16;
+            if (e && f - c0 < 64u) bf = base + (uint32_t)__builtin_popcountll(bm & ((1ull << (f - c0)) - 1ull));
+            if (e && e - c0 - 1u < 64u) be = base + (uint32_t)__builtin_popcountll(bm & (~0ull >> (64u - (e - c0))));
+            base += (uint32_t)__builtin_popcountll(bm);
+            x0 = x1, x1 = x2, h = h1;
+        }
+        if (k < n) {
+            uint32_t *p = ps + (size_t)k * kPassWords;
+            p[kPsMatch] += mt;
+            p[kPsMismatch] += hb - mt;
+            p[kPsIns] += ins;
+            if (be > bf) {  // the span holds base columns: every one without a base of the read is a deletion
+                p[kPsDel] += be - bf - hb;
+                if (p[kPsCend] == 0) p[kPsCbeg] = ol + bf;  // (cend >= 1 once a column was spanned)
+                p[kPsCend] = ol + be;
+            }
+        }
+    }
+}
+
 // emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag.
-// qual (KArgs::qual, may be null): the quality byte of every base written
+// qual (KArgs::qual, may be null): the quality byte of every base written;
+// PS (the pass-statistics kernels, KArgs::pstat set): the reads' pass records
+// take these columns
+template <bool PS>
 __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
                                      uint32_t &ol)
 {
+    if constexpr (PS) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
     uint8_t *qual = a.qual ? a.qual + z.d.out_off : nullptr;
     const uint32_t lane = lane_id(), nw = z.d.nw;
     const uint8_t *cons = P<uint8_t>(z, z.L.cons);
@@ -3132,7 +3241,12 @@ __device__ __forceinline__ void write_msa(Z &z, uint32_t ncols, uint32_t n, uint
 // RD_HBM: the instance for ZMWs whose reads do not fit the LDS read buffer
 // (or whose cursors do not): the read (nibble pairs) and the shredding cursors
 // live in the workspace; every other access is the same code.
-template <bool RD_HBM>
+// PS: the instance that also keeps the pass records (SPEC.md §10, KArgs::pstat
+// set).  A kernel of its own rather than a branch on the pointer, so that the
+// kernels every other launch runs are compiled from exactly the code they were
+// before (the branch alone moved the register allocation of the whole kernel:
+// +0.2 % per launch with the feature off).
+template <bool RD_HBM, bool PS>
 __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
 {
     if (blockIdx.x >= a.nzmw) return;
@@ -3186,6 +3300,12 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
     uint32_t *rdoff = P<uint32_t>(z, z.L.rdoff), *rdlen = P<uint32_t>(z, z.L.rdlen);
     uint8_t *out = a.out + z.d.out_off;
     uint32_t ol = 0;
+    if constexpr (PS) {
+        // the pass records accumulate over the emit calls: a slice launched again starts from zero
+        uint32_t *ps = a.pstat + (size_t)z.d.seg0 * kPassWords;
+        for (uint32_t x = lane; x < n * kPassWords; x += 64) ps[x] = 0;
+        wsync();
+    }
 
     if (a.mode != kShred) {
         // ccs_for (main.c:486-502) / single bspoa call: push every segment whole
@@ -3193,7 +3313,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit(z, ncols, ncols, n, false, out, a, ol);
+            emit<PS>(z, ncols, ncols, n, false, out, a, ol);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3243,7 +3363,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit(z, i, ncols, n, flag, out, a, ol);
+            emit<PS>(z, i, ncols, n, flag, out, a, ol);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {
@@ -3269,7 +3389,14 @@ __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per
 ccsx_zmw_kernel(KArgs a)
 {
     extern __shared__ int32_t smem[];
-    zmw_body<false>(a, smem);
+    zmw_body<false, false>(a, smem);
+}
+
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_ps(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<false, true>(a, smem);
 }
 
 #ifndef CCSX_RING16  // (solo16 takes LDS-instance slices only: ccsx_gpu.cpp stage_slot)
@@ -3277,7 +3404,14 @@ __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per
 ccsx_zmw_kernel_hbm(KArgs a)
 {
     extern __shared__ int32_t smem[];
-    zmw_body<true>(a, smem);
+    zmw_body<true, false>(a, smem);
+}
+
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_hbm_ps(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<true, true>(a, smem);
 }
 #endif
 
@@ -3302,24 +3436,18 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
 {
     namespace K = ccsx::CCSX_KCFG;
     if (lds_bytes < (uint32_t)K::kLdsFixed * 4u) return hipErrorInvalidValue;
+    // KArgs::pstat selects the pass-statistics kernels
+    void (*k)(ccsx::KArgs) = a->pstat ? &K::ccsx_zmw_kernel_ps : &K::ccsx_zmw_kernel;
 #ifdef CCSX_RING16
     if (!a->lds_read_words) return hipErrorInvalidValue;
-    const void *f = reinterpret_cast<const void *>(&K::ccsx_zmw_kernel);
 #else
-    const void *f = a->lds_read_words ? reinterpret_cast<const void *>(&K::ccsx_zmw_kernel)
-                                      : reinterpret_cast<const void *>(&K::ccsx_zmw_kernel_hbm);
+    if (!a->lds_read_words) k = a->pstat ? &K::ccsx_zmw_kernel_hbm_ps : &K::ccsx_zmw_kernel_hbm;
 #endif
     if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-#ifdef CCSX_RING16
-    hipLaunchKernelGGL(K::ccsx_zmw_kernel, dim3(a->nzmw), dim3(K::kBlockThreads), lds_bytes, s, *a);
-#else
-    if (a->lds_read_words)
-        hipLaunchKernelGGL(K::ccsx_zmw_kernel, dim3(a->nzmw), dim3(K::kBlockThreads), lds_bytes, s, *a);
-    else
-        hipLaunchKernelGGL(K::ccsx_zmw_kernel_hbm, dim3(a->nzmw), dim3(K::kBlockThreads), lds_bytes, s, *a);
-#endif
+    hipLaunchKernelGGL(k, dim3(a->nzmw), dim3(K::kBlockThreads), lds_bytes, s, *a);
     return hipGetLastError();
 }

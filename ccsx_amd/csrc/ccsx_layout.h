@@ -126,6 +126,10 @@ CCSX_HD inline uint8_t qual_phred(uint32_t match, uint32_t cov)
     return uint8_t(q < kQMin ? kQMin : q > kQMax ? kQMax : q);
 }
 
+// Per-pass alignment statistics (SPEC.md §10): one record per pushed segment,
+// the words of ccsx_pass_stat (ccsx_gpu.h) in its order
+enum PassWord : uint32_t { kPsMatch = 0, kPsMismatch, kPsIns, kPsDel, kPsCbeg, kPsCend, kPassWords };
+
 // The extension regions, in order (offsets relative to ZLayout::ext):
 //  * the far rows' slot records (rows with more than four predecessors or one
 //    beyond the DP ring, whose 8-bit cell records carry no tags): per cell the
@@ -269,6 +273,7 @@ struct KArgs {
     unsigned long long *prof;  // optional: kProfSlots shader-clock counters per ZMW (diagnostics)
     uint32_t *bplog;           // optional: per-round breakpoint log (main.c:619-620, ZmwDesc::bp_off)
     uint8_t *qual;             // optional: a quality byte (0..kQMax, not ASCII) per CCS byte, same offsets as out
+    uint32_t *pstat;           // optional: kPassWords words per segment at (ZmwDesc::seg0 + k) * kPassWords (SPEC.md §10)
 };
 
 // phase counters written when KArgs::prof != nullptr

@@ -122,6 +122,7 @@ struct Zmw {
     std::string ccs;
     std::string qual;         // -q: the CCS bases' qualities, Q + 33
     double rq = 0;            // -q: predicted accuracy of the read (ccsx_qual_rq)
+    std::vector<ccsx_pass_stat> pst;  // -r: one record per segment (SPEC.md section 10)
     int32_t status = 0;
     std::vector<uint32_t> bp;  // -v >= 3: (breakpoint, MSA columns) per shredding round
 };
@@ -165,6 +166,7 @@ int usage()
             "-A             For fasta/fastq input,gzip allowed  \n"
             "-P             primitive bsalign,subread shred by default \n"
             "-q             Output fastq: per-base consensus qualities (Q+33), np= and rq= in the header \n"
+            "-r     <file>  Pass report (tab-separated): per subread, its match/mismatch/ins/del counts against the CCS, the CCS stretch it covers, identity \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
             "\n"
@@ -459,16 +461,18 @@ int main(int argc, char **argv)
     }
     int c, verbose = 0, min_subread_len = 5000, max_subread_len = 500000, min_fulllen_count = 3, nthreads = 1;
     int isbam = 1, split_subread = 1, fastq = 0;
+    const char *report_path = nullptr;  // -r
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvq")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
         case 'P': split_subread = 0; break;
         case 'A': isbam = 0; break;
         case 'q': fastq = 1; break;
+        case 'r': report_path = optarg; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -511,6 +515,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
+    FILE *fp_rep = report_path ? fopen(report_path, "w") : nullptr;
+    if (report_path && !fp_rep) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    if (fp_rep) fprintf(fp_rep, "#name\tpass\tsbeg\tslen\tmatch\tmismatch\tins\tdel\tcbeg\tcend\tidentity\n");
     // step 1 pipelined per context (ccsx_gpu_submit / ccsx_gpu_collect: the
     // next batch is launched before the previous one is collected);
     // CCSX_ASYNC=0: one ccsx_gpu_run per batch (also for the -v >= 3
@@ -610,7 +620,7 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
-        bool qfail = false;  // -q: the batch's qualities are missing (a context error)
+        bool qfail = false;  // -q / -r: the batch's qualities or pass records are missing (a context error)
         if (r == 0 || r == -2) {
             // -2: some ZMWs failed on the device, the rest are valid
             uint64_t cells = 0;
@@ -631,6 +641,15 @@ int main(int argc, char **argv)
                     z.rq = ccsx_qual_rq(q, ql);
                     z.qual.resize(ql);
                     for (uint32_t k = 0; k < ql; ++k) z.qual[k] = (char)(q[k] + 33);
+                }
+                if (fp_rep && !f.out[i].status) {
+                    const ccsx_pass_stat *st = nullptr;
+                    uint32_t ns = 0;
+                    if (ccsx_gpu_pass_stats(ctx[w], f.slot, i, &st, &ns) != 0 || ns != z.seg_len.size()) {
+                        qfail = true;
+                        break;
+                    }
+                    z.pst.assign(st, st + ns);
                 }
                 const uint32_t *lg;
                 uint32_t nr = 0;
@@ -826,6 +845,7 @@ int main(int argc, char **argv)
             ccsx_gpu_set_prealloc(ctx[i], 1);
             if (verbose > 2 && split_subread) ccsx_gpu_set_bp_log(ctx[i], 1);
             if (fastq) ccsx_gpu_set_quality(ctx[i], 1);
+            if (fp_rep) ccsx_gpu_set_pass_stats(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
@@ -887,6 +907,13 @@ int main(int argc, char **argv)
                                 z.seg_len.size(), z.rq, z.ccs.c_str(), z.qual.c_str());
                     else
                         fprintf(fp_out, ">%s/%s/ccs\n%s\n", z.movie.c_str(), z.hole.c_str(), z.ccs.c_str());
+                    if (fp_rep)
+                        for (size_t k = 0; k < z.pst.size(); ++k) {
+                            const ccsx_pass_stat &p = z.pst[k];
+                            fprintf(fp_rep, "%s/%s/ccs\t%zu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%.6f\n", z.movie.c_str(),
+                                    z.hole.c_str(), k, z.seg_off[k], z.seg_len[k], p.match, p.mismatch, p.ins, p.del, p.cbeg,
+                                    p.cend, ccsx_pass_identity(&p));
+                        }
                 }
             }
             if (timing) fprintf(stderr, "[ccsx] chunk %zu written at %.0f ms\n", ch->id, now_ms());
@@ -960,6 +987,7 @@ int main(int argc, char **argv)
         // or the last chunk; process exit releases both
         // a failed final write (ENOSPC, EPIPE on a FIFO) must not exit 0
         bool werr = fp_out != stdout && (ferror(fp_out) || fclose(fp_out) != 0);
+        if (fp_rep) werr = (ferror(fp_rep) || fclose(fp_rep) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -999,6 +1027,7 @@ int main(int argc, char **argv)
     rd.reset();
     if (fp_out != stdout) (void)fclose(fp_out);
     else (void)fflush(stdout);
+    if (fp_rep) (void)fclose(fp_rep);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

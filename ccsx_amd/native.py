@@ -30,10 +30,10 @@ EXPORTS = {
                    "ccsx_gpu_run_stats", "ccsx_gpu_zmw_bytes", "ccsx_gpu_set_slot_budget", "ccsx_gpu_set_wg_cap",
                    "ccsx_gpu_set_shred_read_cap", "ccsx_gpu_set_mem_frac", "ccsx_gpu_set_mem_wait",
                    "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
-                   "ccsx_gpu_set_quality", "ccsx_gpu_quality"],
+                   "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
-                    "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq",
+                    "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
                     "ccsx_synth_batch_make", "ccsx_synth_batch_zmws", "ccsx_synth_batch_free"],
     "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_close"],
 }
@@ -96,10 +96,12 @@ def lib() -> C.CDLL:
         L.ccsx_gpu_set_shred_read_cap.argtypes = [C.c_void_p, C.c_uint32]
         L.ccsx_gpu_set_mem_share.argtypes = [C.c_void_p, C.c_uint32]
         L.ccsx_gpu_set_mem_frac.argtypes = [C.c_void_p, C.c_float]
-        L.ccsx_gpu_set_mem_wait.argtypes = [C.c_void_p, C.c_uint32]
+        if hasattr(L, "ccsx_gpu_set_mem_wait"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_gpu_set_mem_wait.argtypes = [C.c_void_p, C.c_uint32]
         L.ccsx_gpu_slot_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.ccsx_gpu_submit.argtypes = [C.c_void_p, C.c_int, C.POINTER(ZmwIn), C.c_size_t, C.POINTER(C.c_int)]
         L.ccsx_gpu_collect.argtypes = [C.c_void_p, C.c_int, C.POINTER(ZmwOut)]
+        L.ccsx_gpu_set_fault.argtypes = [C.c_void_p, C.c_int64]
         L.ccsx_gpu_set_bp_log.argtypes = [C.c_void_p, C.c_int]
         L.ccsx_gpu_bp_log.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint32)),
                                       C.POINTER(C.c_uint32)]
@@ -111,6 +113,12 @@ def lib() -> C.CDLL:
             L.ccsx_qual_phred.restype = C.c_uint8
             L.ccsx_qual_rq.argtypes = [C.c_void_p, C.c_uint32]
             L.ccsx_qual_rq.restype = C.c_double
+        if hasattr(L, "ccsx_gpu_set_pass_stats"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_gpu_set_pass_stats.argtypes = [C.c_void_p, C.c_int]
+            L.ccsx_gpu_pass_stats.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_uint32)]
+            L.ccsx_pass_identity.argtypes = [C.c_void_p]
+            L.ccsx_pass_identity.restype = C.c_double
         L.ccsx_revcomp.argtypes = [C.c_char_p, C.c_uint32]
         L.ccsx_prepare.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
@@ -238,6 +246,14 @@ def qual_rq(qual) -> float:
     q = np.ascontiguousarray(np.frombuffer(qual, dtype=np.uint8) if isinstance(qual, (bytes, bytearray)) else
                              np.asarray(qual, dtype=np.uint8))
     return float(lib().ccsx_qual_rq(q.ctypes.data, len(q)))
+
+
+def pass_identity(rec) -> float:
+    """ccsx_pass_identity: match / (match + mismatch + ins + del) of one pass
+    record (match, mismatch, ins, del, cbeg, cend; SPEC.md §10), 0.0 for an
+    empty one."""
+    r = np.ascontiguousarray(np.asarray(rec, dtype=np.uint32).reshape(6))
+    return float(lib().ccsx_pass_identity(r.ctypes.data))
 
 
 def read_calls(path: str, is_bam: bool = False):
@@ -487,6 +503,32 @@ class Engine:
         if self._L.ccsx_gpu_quality(self._ctx, slot, i, C.byref(p), C.byref(n)) != 0:
             self._err("ccsx_gpu_quality")
         return C.string_at(p, n.value) if n.value else b""
+
+    def set_pass_stats(self, on: bool = True) -> None:
+        """Per-pass alignment statistics for the following stage / run / submit
+        calls (ccsx_gpu_set_pass_stats): one record per segment, read with
+        pass_stats()."""
+        if self._L.ccsx_gpu_set_pass_stats(self._ctx, 1 if on else 0) != 0:
+            self._err("ccsx_gpu_set_pass_stats")
+
+    def pass_stats(self, i: int, slot: int = -1) -> np.ndarray:
+        """The pass records of ZMW i, uint32 [nseg, 6] = match, mismatch, ins,
+        del, cbeg, cend per segment in push order: of the last run() / fetch()
+        (slot -1) or of the batch collected from `slot`; raises if that batch
+        ran with pass statistics off or the ZMW failed."""
+        p = C.c_void_p()
+        n = C.c_uint32(0)
+        if self._L.ccsx_gpu_pass_stats(self._ctx, slot, i, C.byref(p), C.byref(n)) != 0:
+            self._err("ccsx_gpu_pass_stats")
+        if not n.value:
+            return np.zeros((0, 6), np.uint32)
+        return np.frombuffer(C.string_at(p, n.value * 24), dtype=np.uint32).reshape(n.value, 6).copy()
+
+    def set_fault(self, i: int) -> None:
+        """Test hook (ccsx_gpu_set_fault): the next run() / submit() reports ZMW
+        i of its batch as failed after computing it; -1 = off."""
+        if self._L.ccsx_gpu_set_fault(self._ctx, i) != 0:
+            self._err("ccsx_gpu_set_fault")
 
     def set_bp_log(self, on: bool = True) -> None:
         """Record the -v >= 3 breakpoint log (main.c:619-620) in ccsx_gpu_run."""

@@ -132,6 +132,32 @@ int ccsx_gpu_bp_log(const ccsx_ctx *ctx, size_t zmw, const uint32_t **pairs, uin
  * them are ccsx_qual_rq (ccsx_host.h) and np = the ZMW's nseg. */
 int ccsx_gpu_set_quality(ccsx_ctx *ctx, int on);
 int ccsx_gpu_quality(ccsx_ctx *ctx, int slot, size_t zmw, const uint8_t **qual, uint32_t *len);
+/* Per-pass alignment statistics (SPEC.md section 10), off by default: how each
+ * pushed segment lies in the MSA its CCS was called from.  on != 0: the
+ * following ccsx_gpu_stage* / ccsx_gpu_run / ccsx_gpu_submit calls give every
+ * ZMW one record per segment, in the order of ccsx_zmw_in::seg_off: 24 bytes
+ * per segment on the device and in the pinned host output, accumulated by the
+ * kernel's emission over the shredding rounds and copied back with the CCS.
+ * With pass statistics on, ccsx_gpu_zmw_bytes, the batch size ccsx_gpu_submit
+ * checks against ccsx_gpu_slot_bytes and ccsx_gpu_staged_bytes include exactly
+ * 24 x nseg per ZMW (a caller sizing ccsx_gpu_reserve_staging adds the same to
+ * its out_bytes); with them off those values, the kernel's work and the bytes
+ * copied are what they are without this call.  Independent of
+ * ccsx_gpu_set_quality.  A batch keeps the setting it was staged or submitted
+ * with (the full-capacity re-run inside ccsx_gpu_collect included).  The
+ * bspoa-compatible single-POA mode (ccsx_bspoa.h) has no pass statistics.
+ * ccsx_gpu_pass_stats: the *nseg records of ZMW `zmw` of a batch: slot -1 =
+ * the last ccsx_gpu_run or ccsx_gpu_fetch on this context, 0 / 1 = that slot's
+ * last collected ccsx_gpu_submit batch.  ctx-owned, valid as long as that
+ * batch's out[i].ccs.  Returns -1 (ccsx_gpu_error says why) if the batch ran
+ * with pass statistics off, is not collected yet, has no ZMW `zmw`, or that
+ * ZMW failed (status != 0).  cbeg / cend are offsets into the ZMW's CCS;
+ * ccsx_pass_identity (ccsx_host.h) derives the identity of a record. */
+typedef struct {
+    uint32_t match, mismatch, ins, del, cbeg, cend;
+} ccsx_pass_stat;
+int ccsx_gpu_set_pass_stats(ccsx_ctx *ctx, int on);
+int ccsx_gpu_pass_stats(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_pass_stat **st, uint32_t *nseg);
 /* The same in three steps (one slice, tight capacities, no re-run), so inputs
  * can stay resident in HBM across launches (used by bench.py).
  * ccsx_gpu_launch returns the kernel time measured with HIP events on the
@@ -146,7 +172,7 @@ int ccsx_gpu_launch(ccsx_ctx *ctx, int mode, float *kernel_ms);
 int ccsx_gpu_fetch(ccsx_ctx *ctx, ccsx_zmw_out *out);
 
 /* Device bytes the staged batch occupies (workspace + arenas; the quality
- * plane when the batch has one). */
+ * plane and the pass records when the batch has them). */
 uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *ctx);
 
 /* Diagnostics: per-phase shader-clock counters (s_memtime) summed over the
@@ -199,7 +225,7 @@ int ccsx_gpu_run_stats(const ccsx_ctx *ctx, uint64_t *stats, uint32_t n);
 int ccsx_gpu_set_mem_wait(ccsx_ctx *ctx, uint32_t ms);
 /* Device bytes ZMW *z occupies in a ccsx_gpu_run slice of `mode` (tight
  * capacities: workspace, subreads, output slab -- twice with quality on --,
- * tables). */
+ * tables, 24 bytes per segment with pass statistics on). */
 uint64_t ccsx_gpu_zmw_bytes(const ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z);
 /* Test hook: bytes per slot for ccsx_gpu_run's slices (0 = by device memory:
  * half of this context's share, ccsx_gpu_set_mem_share), so a small batch is

@@ -61,6 +61,11 @@ uint32_t ccsx_partition(const uint64_t *cost, uint32_t n, uint32_t nparts, uint3
 uint8_t ccsx_qual_phred(uint32_t match, uint32_t cov);
 double ccsx_qual_rq(const uint8_t *qual, uint32_t len);
 
+/* Identity of one pass against the consensus (SPEC.md section 10), from its
+ * record (ccsx_gpu_pass_stats): match / (match + mismatch + ins + del) in
+ * double; 0.0 when the record is empty (or st is NULL). */
+double ccsx_pass_identity(const ccsx_pass_stat *st);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
