@@ -404,6 +404,31 @@ class Engine:
         return [(C.string_at(out[i].ccs, out[i].len) if out[i].len else b"", out[i].status, out[i].cells)
                 for i in range(len(zmws))]
 
+    def single_poa(self, reads: list[bytes]):
+        """One POA of `reads` on this context (ccsx_gpu_single_poa, the path
+        of the bspoa-compatible API; a forced kernel object applies): returns
+        (consensus codes uint8 [ncns], tidy MSA uint8 [ncols, nseq + 4])."""
+        fn = self._L.ccsx_gpu_single_poa
+        fn.argtypes = [C.c_void_p, C.POINTER(ZmwIn), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
+                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        offs, o = [], 0
+        for r in reads:
+            offs.append(o)
+            o += len(r)
+        arr, keep = self._build_in([Prepared(b"".join(reads), _u32(offs), _u32([len(r) for r in reads]))])
+        cns, msa = C.c_void_p(), C.c_void_p()
+        ncns, ncols = C.c_uint32(0), C.c_uint32(0)
+        if fn(self._ctx, arr, C.byref(cns), C.byref(ncns), C.byref(msa), C.byref(ncols)) != 0:
+            self._err("ccsx_gpu_single_poa")
+        self._nz = 1
+        mrow = len(reads) + 4
+        # (the engine returns the consensus as letters; bspoa's g->cns holds codes)
+        letters = C.string_at(cns, ncns.value) if ncns.value else b""
+        c = np.frombuffer(letters.translate(bytes.maketrans(b"ACGT", bytes(range(4)))), dtype=np.uint8).copy()
+        m = (np.frombuffer(C.string_at(msa, ncols.value * mrow), dtype=np.uint8).reshape(ncols.value, mrow).copy()
+             if ncols.value else np.zeros((0, mrow), np.uint8))
+        return c, m
+
     def run_batch(self, batch: "SynthBatch", mode: int = MODE_SHRED, keep=()):
         """ccsx_gpu_run on a synthetic batch; returns [(status, cells, len)]
         and, when `keep` lists batch indices, also {index: CCS bytes}."""

@@ -61,8 +61,83 @@ def lib() -> C.CDLL:
         L.oprep_prepare_apply.restype = C.c_uint32
         L.oprep_pairwise.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32]
         L.oprep_pairwise.restype = OprepAln
+        for f in ("opoa_row_kinds", "opoa_tb_moves", "opoa_tb_hist", "opoa_band_hist", "opoa_tb_events",
+                  "opoa_tie_hist"):
+            getattr(L, f).argtypes = [C.POINTER(C.c_uint64), C.c_int]
+            getattr(L, f).restype = None
+        L.opoa_set_counting.argtypes = [C.c_int]
+        L.opoa_set_counting.restype = None
         _lib = L
     return _lib
+
+
+# ------------------------------------------------------- debug counters
+# Process-wide counters of oracle/poa_oracle.c, summed over every DP and
+# traceback since the last reset.  Read them single-threaded, around Poa calls
+# (never around batch(), whose threads would race on them).  tb_hist,
+# band_hist, tb_events and tie_hist count only inside `with counting():`.
+TB_STATES = ("M", "D")
+TB_CLASSES = ("np1", "np2", "np3_4", "np5+")  # the moved-from row's predecessor count
+TB_RES = 32                                   # ... its index mod 32
+TB_DIST = 35                                  # distance bins: d for 1..33, 34 = longer
+BAND_BINS = ("shift_neg", "shift_0", "shift_1", "shift_2", "shift_3_63", "shift_ge64", "clamp_lo", "clamp_hi",
+             "clamp_short", "partial", "rows", "dps")
+TB_EVENTS = ("tracebacks", "lead", "msrc0", "trail_ins", "iext_chain", "dext_chain")
+TIES = ("rmax", "rarg", "mh", "src", "dpred", "dext", "dm", "ins", "iext", "end", "best", "gap")
+
+
+def _counter(fn: str, n: int, reset: bool) -> np.ndarray:
+    out = np.zeros(n, np.uint64)
+    getattr(lib(), fn)(out.ctypes.data_as(C.POINTER(C.c_uint64)), 1 if reset else 0)
+    return out
+
+
+def tb_hist(reset: bool = False) -> np.ndarray:
+    """Traceback predecessor moves, uint64 [state, class, row mod 32, distance
+    bin] (TB_STATES, TB_CLASSES, TB_RES, TB_DIST)."""
+    return _counter("opoa_tb_hist", len(TB_STATES) * len(TB_CLASSES) * TB_RES * TB_DIST, reset).reshape(
+        len(TB_STATES), len(TB_CLASSES), TB_RES, TB_DIST)
+
+
+def band_hist(reset: bool = False) -> dict:
+    """DP rows by band shift off_r - off_{r-1}, by the §3.1 clamp that acted
+    (at 0, at m - W, at 0 from above for reads within one band), rows whose
+    band holds cells with j >= m, all rows, DPs (BAND_BINS)."""
+    return dict(zip(BAND_BINS, (int(x) for x in _counter("opoa_band_hist", len(BAND_BINS), reset))))
+
+
+def tb_events(reset: bool = False) -> dict:
+    """Tracebacks, and those with LEAD events (MSRC at j > 0), MSRC at j = 0,
+    trailing INS after the end cell; iext and D-ext chains of length >= 2
+    (TB_EVENTS)."""
+    return dict(zip(TB_EVENTS, (int(x) for x in _counter("opoa_tb_events", len(TB_EVENTS), reset))))
+
+
+def tie_hist(reset: bool = False) -> dict:
+    """Comparisons with equal operands, by the SPEC.md tie rule that settles
+    them (TIES): §3.1 rmax / rarg, §3.2 mh / src / dpred / dext / dm, §3.4
+    ins / iext, §3.5 end, §6 best / gap."""
+    return dict(zip(TIES, (int(x) for x in _counter("opoa_tie_hist", len(TIES), reset))))
+
+
+class counting:
+    """Context manager: zero every debug counter and count until the exit."""
+
+    def __enter__(self):
+        reset_counters()
+        lib().opoa_set_counting(1)
+        return self
+
+    def __exit__(self, *exc):
+        lib().opoa_set_counting(0)
+        return False
+
+
+def reset_counters() -> None:
+    """Zero every debug counter."""
+    _counter("opoa_row_kinds", 8, True)
+    _counter("opoa_tb_moves", 12, True)
+    tb_hist(True), band_hist(True), tb_events(True), tie_hist(True)
 
 
 class OprepAln(C.Structure):

@@ -190,6 +190,67 @@ void opoa_tb_moves(uint64_t *out, int reset)
     if (reset) memset(tb_moves, 0, sizeof tb_moves);
 }
 
+/* Debug statistics for the coverage tables of tests/test_record_cases.py: the
+ * same process-wide, resettable kind of counter as the two above, but with no
+ * kernel ring length built in.  These four (tb_hist, band_hist, tb_events,
+ * tie_hist) count only while switched on (opoa_set_counting; off by default):
+ * the tie counters sit in the DP's inner loop, where ocsx_batch's threads
+ * would contend for them, so dp_align is compiled twice, with and without. */
+static int counting;
+void opoa_set_counting(int on) { counting = on != 0; }
+
+/* opoa_tb_hist: every predecessor move of the traceback by state (0 = M move,
+ * 1 = D move), the moved-from row's predecessor-count class (0: one, 1: two,
+ * 2: three or four, 3: more than four), that row's index mod 32 (its place in
+ * a 32-row traceback block) and the exact row distance (bin d for d = 1..33,
+ * bin 34 for longer ones; bin 0 stays empty). */
+enum { TBH_STATES = 2, TBH_CLASSES = 4, TBH_RES = 32, TBH_DIST = 35 };
+static uint64_t tb_hist[TBH_STATES][TBH_CLASSES][TBH_RES][TBH_DIST];
+void opoa_tb_hist(uint64_t *out, int reset)
+{
+    memcpy(out, tb_hist, sizeof tb_hist);
+    if (reset) memset(tb_hist, 0, sizeof tb_hist);
+}
+
+/* opoa_band_hist: per DP row with predecessors, off_r - off_{r-1} (SPEC.md
+ * §3.1) in the bins < 0, 0, 1, 2, 3..63, >= 64; whether the clamp acted at 0,
+ * at m - W (reads longer than the band) or at 0 from above (reads of at most
+ * W bases, where m - W counts as 0); rows whose band holds invalid cells
+ * (j >= m); all DP rows; DPs. */
+enum { BH_NEG, BH_0, BH_1, BH_2, BH_3_63, BH_GE64, BH_CLAMP_LO, BH_CLAMP_HI, BH_CLAMP_SHORT, BH_PARTIAL, BH_ROWS,
+       BH_DPS, BH_N };
+static uint64_t band_hist[BH_N];
+void opoa_band_hist(uint64_t *out, int reset)
+{
+    memcpy(out, band_hist, sizeof band_hist);
+    if (reset) memset(band_hist, 0, sizeof band_hist);
+}
+
+/* opoa_tb_events: tracebacks; those that ended in MSRC with j > 0 (LEAD
+ * events) and with j = 0; those that emitted trailing INS after the end cell;
+ * runs of two or more I steps (iext chains) and of two or more D moves (D-ext
+ * chains). */
+enum { TE_TRACEBACKS, TE_LEAD, TE_MSRC0, TE_TRAIL_INS, TE_IEXT2, TE_DEXT2, TE_N };
+static uint64_t tb_events[TE_N];
+void opoa_tb_events(uint64_t *out, int reset)
+{
+    memcpy(out, tb_events, sizeof tb_events);
+    if (reset) memset(tb_events, 0, sizeof tb_events);
+}
+
+/* opoa_tie_hist: how often a comparison that SPEC.md settles by a tie rule met
+ * equal operands: §3.1 equal row maxima among predecessors / within the row;
+ * §3.2 Mh among predecessors, Mh = src, D candidates among predecessors,
+ * a = b (the D-ext bit), D = M; §3.4 I = H', and the two prefix maxima of
+ * iext; §3.5 equal end scores; §6 equal best counts, and cnt[best] = gap > 0. */
+enum { TI_RMAX, TI_RARG, TI_MH, TI_SRC, TI_DPRED, TI_DEXT, TI_DM, TI_INS, TI_IEXT, TI_END, TI_BEST, TI_GAP, TI_N };
+static uint64_t tie_hist[TI_N];
+void opoa_tie_hist(uint64_t *out, int reset)
+{
+    memcpy(out, tie_hist, sizeof tie_hist);
+    if (reset) memset(tie_hist, 0, sizeof tie_hist);
+}
+
 static void count_tb_move(const graph_t *G, uint32_t r, uint32_t p, int isD)
 {
     const uint32_t np = G->poff[r + 1] - G->poff[r];
@@ -202,6 +263,7 @@ static void count_tb_move(const graph_t *G, uint32_t r, uint32_t p, int isD)
     if (isD && far) tb_moves[TB_DDFAR]++;
     if (!isD && !far && d == 4) tb_moves[TB_M4]++;
     if (!isD && !far && d > 4) tb_moves[TB_M5_8]++;
+    if (counting) tb_hist[isD ? 1 : 0][np == 1 ? 0 : np == 2 ? 1 : np <= 4 ? 2 : 3][r % TBH_RES][d < TBH_DIST - 1 ? d : TBH_DIST - 1]++;
 }
 
 static void count_row_kind(const graph_t *G, uint32_t r, int32_t off, int32_t poff, const uint8_t *spill)
@@ -222,7 +284,8 @@ static void count_row_kind(const graph_t *G, uint32_t r, int32_t off, int32_t po
 }
 
 /* SPEC.md §3: banded read-vs-graph DP, rows in graph row order. */
-static void dp_align(opoa_t *g, const uint8_t *q, uint32_t m, uint32_t *er_out, uint32_t *ej_out)
+static inline __attribute__((always_inline)) void dp_align_impl(opoa_t *g, const uint8_t *q, uint32_t m,
+                                                                uint32_t *er_out, uint32_t *ej_out, const int CNT)
 {
     const graph_t *G = &g->g;
     const int W = g->W, O = g->O, E = g->E;
@@ -255,12 +318,22 @@ static void dp_align(opoa_t *g, const uint8_t *q, uint32_t m, uint32_t *er_out, 
         if (np) {
             int32_t bm = INT32_MIN;
             uint32_t bp = 0;
-            for (uint32_t s = 0; s < np; ++s)
+            for (uint32_t s = 0; s < np; ++s) {
+                if (CNT && s && g->rmax[pl[s]] == bm) tie_hist[TI_RMAX]++;
                 if (g->rmax[pl[s]] > bm) bm = g->rmax[pl[s]], bp = pl[s];
+            }
             off = g->rarg[bp] + 1 - W / 2;
+            if (CNT && off < 0) band_hist[BH_CLAMP_LO]++;
+            else if (CNT && off > lim) band_hist[m > (uint32_t)W ? BH_CLAMP_HI : BH_CLAMP_SHORT]++;
             if (off < 0) off = 0;
             if (off > lim) off = lim;
+            if (CNT && r) {
+                const int32_t sh = off - g->roff[r - 1];
+                band_hist[sh < 0 ? BH_NEG : sh == 0 ? BH_0 : sh == 1 ? BH_1 : sh == 2 ? BH_2 : sh < 64 ? BH_3_63 : BH_GE64]++;
+            }
         }
+        if (CNT) band_hist[BH_ROWS]++;
+        if (CNT && (int64_t)off + W > (int64_t)m) band_hist[BH_PARTIAL]++;
         g->roff[r] = off;
         count_row_kind(G, r, off, r ? g->roff[r - 1] : 0, spill);
         int32_t *H = g->Hs + (size_t)r * W, *D = g->Ds + (size_t)r * W;
@@ -278,11 +351,13 @@ static void dp_align(opoa_t *g, const uint8_t *q, uint32_t m, uint32_t *er_out, 
             uint32_t msl = 0;
             for (uint32_t s = 0; s < np; ++s) {
                 int32_t h = getH(g, pl[s], j - 1);
+                if (CNT && h == Mh && h > NEG / 2) tie_hist[TI_MH]++;
                 if (h > Mh) Mh = h, msl = s;
             }
             const int32_t src = j == 0 ? 0 : O + E * (int32_t)j;
             int hc;
             int32_t mb;
+            if (CNT && Mh == src) tie_hist[TI_SRC]++;
             if (Mh >= src) mb = Mh, hc = HC_MPRED;
             else mb = src, hc = HC_MSRC, msl = 0;
             const int32_t Mv = mb + (base == q[j] ? g->M : g->X);
@@ -293,9 +368,12 @@ static void dp_align(opoa_t *g, const uint8_t *q, uint32_t m, uint32_t *er_out, 
                 int32_t a = getH(g, pl[s], j) + O + E;
                 int32_t b = getD(g, pl[s], j) + E;
                 int32_t c = b > a ? b : a;
+                if (CNT && a == b && a > NEG / 2) tie_hist[TI_DEXT]++;
+                if (CNT && c == Dv && c > NEG / 2) tie_hist[TI_DPRED]++;
                 if (c > Dv) Dv = c, dsl = s, dx = b > a;
             }
             int32_t hp = Mv;
+            if (CNT && Dv == Mv) tie_hist[TI_DM]++;
             if (Dv > Mv) hp = Dv, hc = HC_DEL;
             Hp[t] = hp;
             Xv[t] = hp - E * t;
@@ -316,20 +394,31 @@ static void dp_align(opoa_t *g, const uint8_t *q, uint32_t m, uint32_t *er_out, 
             const int32_t I = t == 0 ? NEG : O + E * t + ex;
             const int iext = t > 0 && ex_prev > Xv[t - 1];
             int32_t h = Hp[t];
+            if (CNT && t > 0 && ex_prev == Xv[t - 1] && ex_prev > NEG / 2) tie_hist[TI_IEXT]++;
+            if (CNT && I == h && h > NEG / 2) tie_hist[TI_INS]++;
             if (I > h) h = I, cd[t] = (uint8_t)((cd[t] & ~3u) | HC_INS);
             cd[t] |= (uint8_t)(iext << 3);
             H[t] = h;
+            if (CNT && h == rm) tie_hist[TI_RARG]++;
             if (h > rm) rm = h, ra = (int32_t)j;
             const int32_t e = h + (j == (int64_t)m - 1 ? 0 : O + E * (int32_t)(m - 1 - j));
+            if (CNT && e == bestE) tie_hist[TI_END]++;
             if (e > bestE) bestE = e, er = r, ej = (uint32_t)j;
         }
         g->rmax[r] = rm;
         g->rarg[r] = ra;
     }
     free(spill);
+    if (CNT) band_hist[BH_DPS]++;
     g->cells += (uint64_t)R * (m < (uint32_t)W ? m : (uint32_t)W);
     *er_out = er;
     *ej_out = ej;
+}
+
+static void dp_align(opoa_t *g, const uint8_t *q, uint32_t m, uint32_t *er_out, uint32_t *ej_out)
+{
+    if (counting) dp_align_impl(g, q, m, er_out, ej_out, 1);
+    else dp_align_impl(g, q, m, er_out, ej_out, 0);
 }
 
 /* SPEC.md §4: traceback into per-read-base events. */
@@ -338,6 +427,8 @@ static void traceback(opoa_t *g, uint32_t m, uint32_t er, uint32_t ej)
     const graph_t *G = &g->g;
     const int W = g->W;
     for (uint32_t jj = ej + 1; jj < m; ++jj) g->ev[jj] = (EV_INS << 30) | er;
+    if (counting) tb_events[TE_TRACEBACKS]++, tb_events[TE_TRAIL_INS] += ej + 1 < m;
+    uint32_t irun = 0, drun = 0; /* debug statistics only */
     uint32_t r = er;
     int64_t j = ej;
     int st = 0; /* 0 = H, 1 = D, 2 = I */
@@ -361,6 +452,7 @@ static void traceback(opoa_t *g, uint32_t m, uint32_t er, uint32_t ej)
             } else if (hc == HC_MSRC) {
                 g->ev[j] = (EV_ALN << 30) | r;
                 for (int64_t jj = 0; jj < j; ++jj) g->ev[jj] = (EV_LEAD << 30) | r;
+                if (counting) tb_events[j > 0 ? TE_LEAD : TE_MSRC0]++;
                 break;
             } else if (hc == HC_DEL) {
                 st = 1;
@@ -372,10 +464,14 @@ static void traceback(opoa_t *g, uint32_t m, uint32_t er, uint32_t ej)
             const uint32_t p = G->pred[G->poff[r] + g->ds[cell]];
             count_tb_move(G, r, p, 1);
             r = p;
+            ++drun;
+            if (st != 1) tb_events[TE_DEXT2] += counting && drun >= 2, drun = 0;
         } else {
             g->ev[j] = (EV_INS << 30) | r;
             st = (c >> 3) & 1 ? 2 : 0;
             --j;
+            ++irun;
+            if (st != 2) tb_events[TE_IEXT2] += counting && irun >= 2, irun = 0;
         }
     }
 }
@@ -531,9 +627,12 @@ static void call_columns(opoa_t *g)
         for (uint32_t k = 0; k < n; ++k)
             if (g->rfirst[k] != NONE && colof[g->rfirst[k]] <= col && col <= colof[g->rlast[k]]) ++cov;
         uint32_t best = 0;
-        for (uint32_t b = 1; b < 4; ++b)
+        for (uint32_t b = 1; b < 4; ++b) {
+            if (counting && cnt[b] == cnt[best] && cnt[b]) tie_hist[TI_BEST]++;
             if (cnt[b] > cnt[best]) best = b;
+        }
         const uint32_t gap = cov - tot;
+        if (counting && cnt[best] == gap && gap) tie_hist[TI_GAP]++;
         const uint8_t cons = cnt[best] >= gap ? (uint8_t)best : 4;
         g->ccons[col] = cons;
         if (cons < 4) g->cns[g->ncns++] = cons;
