@@ -265,6 +265,7 @@ struct ccsx_ctx {
     uint32_t shred_read_cap = 4096;
     uint32_t ncu = 256;                // compute units of the device
     uint64_t reruns = 0;               // ZMWs ccsx_gpu_run re-ran with full caps
+    uint64_t hbm_launches = 0;         // slices launched on the HBM-read kernel instance (lds_read_words = 0)
     uint64_t slices = 0;               // slices ccsx_gpu_run launched
     uint64_t dealt = 0, parts = 0;     // lists ccsx_gpu_run dealt into interleaved parts, and their parts
     bool profiling = false;
@@ -764,6 +765,7 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     a.nzmw = uint32_t(s.nz);
     a.lds_read_words = s.lds_read_words;
     a.lds_nmax = s.lds_nmax;
+    if (!s.lds_read_words) ++c->hbm_launches;
     a.prof = nullptr;
     a.bplog = s.bp_words ? s.d_bp.as<uint32_t>() : nullptr;
     a.qual = s.qual ? s.d_out.as<uint8_t>() + s.out_bytes : nullptr;
@@ -1470,6 +1472,8 @@ int ccsx_gpu_set_kernel_cfg(ccsx_ctx *c, int cfg)
 int ccsx_gpu_kernel_cfg(const ccsx_ctx *c) { return c ? c->slot[0].cfg : -1; }
 
 int64_t ccsx_gpu_rerun_count(const ccsx_ctx *c) { return c ? (int64_t)c->reruns : -1; }
+
+int64_t ccsx_gpu_hbm_launches(const ccsx_ctx *c) { return c ? (int64_t)c->hbm_launches : -1; }
 
 int ccsx_gpu_run_stats(const ccsx_ctx *c, uint64_t *st, uint32_t n)
 {

@@ -25,7 +25,7 @@ EXPORTS = {
                    "ccsx_gpu_stage", "ccsx_gpu_launch", "ccsx_gpu_fetch", "ccsx_gpu_staged_bytes",
                    "ccsx_gpu_set_profiling", "ccsx_gpu_profile", "ccsx_gpu_profile_zmw", "ccsx_gpu_set_tight_rows", "ccsx_gpu_set_tight_out", "ccsx_gpu_set_tight_far", "ccsx_gpu_set_stage_piece",
                    "ccsx_gpu_set_mem_share", "ccsx_gpu_set_prealloc", "ccsx_gpu_set_fault",
-                   "ccsx_gpu_set_kernel_cfg", "ccsx_gpu_kernel_cfg", "ccsx_gpu_rerun_count",
+                   "ccsx_gpu_set_kernel_cfg", "ccsx_gpu_kernel_cfg", "ccsx_gpu_rerun_count", "ccsx_gpu_hbm_launches",
                    "ccsx_gpu_set_bp_log", "ccsx_gpu_bp_log", "ccsx_gpu_stage_for",
                    "ccsx_gpu_run_stats", "ccsx_gpu_zmw_bytes", "ccsx_gpu_set_slot_budget", "ccsx_gpu_set_wg_cap",
                    "ccsx_gpu_set_shred_read_cap", "ccsx_gpu_set_mem_frac", "ccsx_gpu_set_mem_wait",
@@ -88,6 +88,8 @@ def lib() -> C.CDLL:
         L.ccsx_gpu_kernel_cfg.argtypes = [C.c_void_p]
         L.ccsx_gpu_rerun_count.argtypes = [C.c_void_p]
         L.ccsx_gpu_rerun_count.restype = C.c_int64
+        L.ccsx_gpu_hbm_launches.argtypes = [C.c_void_p]
+        L.ccsx_gpu_hbm_launches.restype = C.c_int64
         L.ccsx_gpu_run_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         L.ccsx_gpu_zmw_bytes.argtypes = [C.c_void_p, C.c_int, C.POINTER(ZmwIn)]
         L.ccsx_gpu_zmw_bytes.restype = C.c_uint64
@@ -465,6 +467,10 @@ class Engine:
     def rerun_count(self) -> int:
         """ZMWs run() has re-run with full caps so far."""
         return int(self._L.ccsx_gpu_rerun_count(self._ctx))
+
+    def hbm_launches(self) -> int:
+        """Slices launched on the HBM-read kernel instance so far."""
+        return int(self._L.ccsx_gpu_hbm_launches(self._ctx))
 
     def run_stats(self) -> dict:
         """ccsx_gpu_run counters so far: reruns, slices, dealt lists, their

@@ -212,6 +212,12 @@ int ccsx_gpu_set_kernel_cfg(ccsx_ctx *ctx, int cfg);
 int ccsx_gpu_kernel_cfg(const ccsx_ctx *ctx);
 /* ZMWs ccsx_gpu_run has re-run with full caps on this context so far. */
 int64_t ccsx_gpu_rerun_count(const ccsx_ctx *ctx);
+/* Slices this context has launched on the HBM-read kernel instance so far (the
+ * read buffer and the shredding cursors in the workspace, not in LDS: a slice
+ * with more than 4,096 segments in a ZMW, or with a segment above 100,000
+ * bases unless it is a tight-cap shredded slice).  Read-only; a full-caps
+ * re-run is a launch of its own, on either slot. */
+int64_t ccsx_gpu_hbm_launches(const ccsx_ctx *ctx);
 /* Counters of this context's ccsx_gpu_run calls so far, the first n of:
  * [0] ZMWs re-run with full caps, [1] slices launched, [2] ZMW lists dealt
  * into interleaved parts (a list of one launch class that needs k > 1 slots),

@@ -62,9 +62,10 @@ def lib() -> C.CDLL:
         L.oprep_pairwise.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32]
         L.oprep_pairwise.restype = OprepAln
         for f in ("opoa_row_kinds", "opoa_tb_moves", "opoa_tb_hist", "opoa_band_hist", "opoa_tb_events",
-                  "opoa_tie_hist"):
+                  "opoa_tie_hist", "opoa_shred_hist"):
             getattr(L, f).argtypes = [C.POINTER(C.c_uint64), C.c_int]
             getattr(L, f).restype = None
+        L.opoa_shred_bins.argtypes = []
         L.opoa_set_counting.argtypes = [C.c_int]
         L.opoa_set_counting.restype = None
         _lib = L
@@ -75,7 +76,7 @@ def lib() -> C.CDLL:
 # Process-wide counters of oracle/poa_oracle.c, summed over every DP and
 # traceback since the last reset.  Read them single-threaded, around Poa calls
 # (never around batch(), whose threads would race on them).  tb_hist,
-# band_hist, tb_events and tie_hist count only inside `with counting():`.
+# band_hist, tb_events, tie_hist and shred_hist count only inside `with counting():`.
 TB_STATES = ("M", "D")
 TB_CLASSES = ("np1", "np2", "np3_4", "np5+")  # the moved-from row's predecessor count
 TB_RES = 32                                   # ... its index mod 32
@@ -84,6 +85,20 @@ BAND_BINS = ("shift_neg", "shift_0", "shift_1", "shift_2", "shift_3_63", "shift_
              "clamp_short", "partial", "rows", "dps")
 TB_EVENTS = ("tracebacks", "lead", "msrc0", "trail_ins", "iext_chain", "dext_chain")
 TIES = ("rmax", "rarg", "mh", "src", "dpred", "dext", "dm", "ins", "iext", "end", "best", "gap")
+# opoa_shred_hist (the enum of oracle/poa_oracle.c, in its order)
+SHRED_BINS = (("rounds_1", "rounds_2", "rounds_3_5", "rounds_ge6",
+               "fin_n_lt3", "fin_empty", "fin_exact", "fin_read0_only", "fin_last_only", "fin_ragged", "notfin_by1",
+               "grow_0", "grow_1", "grow_2", "grow_ge3", "grow_found", "grow_final", "push_gt4096",
+               "d0", "d1_62", "d63", "d64", "d65", "d66_126", "d127", "d128", "d_ge129", "d_gt1000",
+               "i_le16", "i_1", "i_2", "none_mult64", "none_lt64",
+               "rej_leadgap", "gap_skip", "rej_nog_lt5", "acc_nog5", "acc_nog6_9", "acc_nog10",
+               "rej_col_by1", "acc_col_eq_n5", "acc_col_eq_n10", "acc_n9_c6", "acc_n9_c7", "rej_n10_c6", "rej_n10_c7",
+               "rej_row_by1", "acc_row_eq_nog5", "acc_row_eq_nog10") +
+              tuple(f"rej_col_off{x}" for x in range(10)) +
+              ("adv_differ", "gapcol_base", "rows_i_ge2", "rows_im1_ge2", "colrow_mod0", "colrow_mod1", "colrow_mod63",
+               "i_mod0", "i_mod1", "i_mod63", "n3", "n9", "n10", "n63", "n64", "n65", "n128", "n129", "nobase",
+               "next_exact", "fin_i_mod0", "fin_i_mod1", "fin_i_mod63",
+               "ccs_cross64", "span_end_edge", "span_beg_edge", "fin_nobase"))
 
 
 def _counter(fn: str, n: int, reset: bool) -> np.ndarray:
@@ -120,6 +135,16 @@ def tie_hist(reset: bool = False) -> dict:
     return dict(zip(TIES, (int(x) for x in _counter("opoa_tie_hist", len(TIES), reset))))
 
 
+def shred_hist(reset: bool = False) -> dict:
+    """What the shredding loop of Poa.zmw / Poa.zmw_breakpoints met (SHRED_BINS;
+    oracle/poa_oracle.c says per bin what is counted): rounds and why the last
+    one is final, window growths, the accepted candidate's depth
+    (ncols - 10) - i, the rule that rejected or accepted each candidate window,
+    the cursor advance and the emitted columns of each round."""
+    assert lib().opoa_shred_bins() == len(SHRED_BINS)
+    return dict(zip(SHRED_BINS, (int(x) for x in _counter("opoa_shred_hist", len(SHRED_BINS), reset))))
+
+
 class counting:
     """Context manager: zero every debug counter and count until the exit."""
 
@@ -137,7 +162,7 @@ def reset_counters() -> None:
     """Zero every debug counter."""
     _counter("opoa_row_kinds", 8, True)
     _counter("opoa_tb_moves", 12, True)
-    tb_hist(True), band_hist(True), tb_events(True), tie_hist(True)
+    tb_hist(True), band_hist(True), tb_events(True), tie_hist(True), shred_hist(True)
 
 
 class OprepAln(C.Structure):

@@ -251,6 +251,48 @@ void opoa_tie_hist(uint64_t *out, int reset)
     if (reset) memset(tie_hist, 0, sizeof tie_hist);
 }
 
+/* opoa_shred_hist: what the shredding loop of ocsx_zmw_log (ccs_for2) met, for
+ * the coverage table of tests/test_shred_cases.py; the bins are SHRED_BINS of
+ * oracle/oracle.py, in this order.  "depth" = (ncols - 10) - i, the number of
+ * candidates the scan rejected before the accepted one.  Counted only while
+ * switched on (opoa_set_counting), and only by ocsx_zmw_log. */
+enum {
+    /* per ZMW: shredding rounds */
+    SH_ROUNDS_1, SH_ROUNDS_2, SH_ROUNDS_3_5, SH_ROUNDS_GE6,
+    /* per final POA call: why it is final (n < 3; a segment of length 0; some read with pos + ws + 1000 == len;
+     * read 0 alone / the last read alone over the limit); remaining lengths <= 1,001 against >= 5,000.
+     * notfinal_by1: a call that is not final with some read one base short of making it final */
+    SH_FIN_NLT3, SH_FIN_EMPTY, SH_FIN_EXACT, SH_FIN_READ0_ONLY, SH_FIN_LAST_ONLY, SH_FIN_RAGGED, SH_NOTFIN_BY1,
+    /* per round: window growths; a growth that ends in a breakpoint / in the final push; a pushed read > 4,096 bases */
+    SH_GROW_0, SH_GROW_1, SH_GROW_2, SH_GROW_GE3, SH_GROW_FOUND, SH_GROW_FINAL, SH_PUSH_GT4096,
+    /* per accepted breakpoint: its depth, a small i; per scan that finds nothing: ncols - 10 a multiple of 64, < 64 */
+    SH_D0, SH_D1_62, SH_D63, SH_D64, SH_D65, SH_D66_126, SH_D127, SH_D128, SH_D_GE129, SH_D_GT1000,
+    SH_I_LE16, SH_I_1, SH_I_2, SH_NONE_MULT64, SH_NONE_LT64,
+    /* per candidate window: the rule that rejected it, or how it was accepted */
+    SH_REJ_LEADGAP, SH_GAP_SKIP, SH_REJ_NOG_LT5, SH_ACC_NOG5, SH_ACC_NOG6_9, SH_ACC_NOG10,
+    SH_REJ_COL_BY1, SH_ACC_COL_EQ_N5, SH_ACC_COL_EQ_N10, SH_ACC_N9_C6, SH_ACC_N9_C7, SH_REJ_N10_C6, SH_REJ_N10_C7,
+    SH_REJ_ROW_BY1, SH_ACC_ROW_EQ_NOG5, SH_ACC_ROW_EQ_NOG10,
+    SH_REJ_COL_OFF0, /* .. SH_REJ_COL_OFF0 + 9: the window offset of the column the column rule rejected */
+    /* per round that advances the cursors (not final), over the emitted columns [0, i) */
+    SH_ADV_DIFFER = SH_REJ_COL_OFF0 + 10, SH_GAPCOL_BASE, SH_ROWS_I_GE2, SH_ROWS_IM1_GE2,
+    SH_COLROW_MOD0, SH_COLROW_MOD1, SH_COLROW_MOD63, SH_I_MOD0, SH_I_MOD1, SH_I_MOD63,
+    SH_N3, SH_N9, SH_N10, SH_N63, SH_N64, SH_N65, SH_N128, SH_N129, SH_NOBASE, SH_NEXT_EXACT,
+    /* per final round: i = ncols mod 64 */
+    SH_FIN_I_MOD0, SH_FIN_I_MOD1, SH_FIN_I_MOD63,
+    /* per round: the emitted CCS crosses a multiple of 64 from an offset that is none; a read's span over the
+     * emitted columns ends before i on a multiple of 64 / begins after column 0 on one; a read without a base
+     * in the emitted columns of a final round */
+    SH_CCS_CROSS64, SH_SPAN_END_EDGE, SH_SPAN_BEG_EDGE, SH_FIN_NOBASE,
+    SH_N
+};
+static uint64_t shred_hist[SH_N];
+void opoa_shred_hist(uint64_t *out, int reset)
+{
+    memcpy(out, shred_hist, sizeof shred_hist);
+    if (reset) memset(shred_hist, 0, sizeof shred_hist);
+}
+int opoa_shred_bins(void) { return SH_N; }
+
 static void count_tb_move(const graph_t *G, uint32_t r, uint32_t p, int isD)
 {
     const uint32_t np = G->poff[r + 1] - G->poff[r];
@@ -451,7 +493,7 @@ static void traceback(opoa_t *g, uint32_t m, uint32_t er, uint32_t ej)
                 --j;
             } else if (hc == HC_MSRC) {
                 g->ev[j] = (EV_ALN << 30) | r;
-                for (int64_t jj = 0; jj < j; ++jj) g->ev[jj] = (EV_LEAD << 30) | r;
+                for (int64_t jj = 0; jj < j; ++jj) g->ev[jj] = ((uint32_t)EV_LEAD << 30) | r;
                 if (counting) tb_events[j > 0 ? TE_LEAD : TE_MSRC0]++;
                 break;
             } else if (hc == HC_DEL) {
@@ -740,6 +782,63 @@ uint32_t opoa_nrows(const opoa_t *g) { return g->g.R; }
 
 static const char BIT_BASE[5] = {'A', 'C', 'G', 'T', 'N'};
 
+/* opoa_shred_hist, one emitted round: columns [0, i) of the current MSA; fin: the final round; ol: the CCS bases
+ * emitted before it; pos / lens: the cursors before the advance */
+static void count_shred_emit(const opoa_t *g, uint32_t n, uint32_t i, int fin, size_t ol, const uint32_t *pos,
+                             const uint32_t *lens)
+{
+    const uint32_t mrow = n + 4;
+    uint64_t rows = 0, rows_i = 0, rows_im1 = 0, emitted = 0;
+    uint32_t *adv = calloc(n ? n : 1, 4);
+    int gapbase = 0;
+    for (uint32_t j = 0; j <= i && j < g->ncols; ++j) {
+        const uint8_t *col = g->msacols + (size_t)g->msaidxs[j] * mrow;
+        uint32_t seen = 0, r = 0;
+        for (uint32_t k = 0; k < n; ++k)
+            if (col[k + 1] < 4) {
+                if (!(seen >> col[k + 1] & 1u)) seen |= 1u << col[k + 1], ++r;
+                if (j < i) ++adv[k], gapbase |= col[n + 1] >= 4;
+            }
+        if (j < i) rows += r, emitted += col[n + 1] < 4;
+        if (j == i) rows_i = r;
+        if (j + 1 == i) rows_im1 = r;
+    }
+    if (!fin) {
+        int differ = 0, nobase = 0, exact = 0;
+        for (uint32_t k = 0; k < n; ++k)
+            differ |= adv[k] != adv[0], nobase |= adv[k] == 0, exact |= pos[k] + adv[k] + 3000 == lens[k];
+        shred_hist[SH_ADV_DIFFER] += differ, shred_hist[SH_GAPCOL_BASE] += gapbase, shred_hist[SH_NOBASE] += nobase;
+        shred_hist[SH_NEXT_EXACT] += exact;
+        shred_hist[SH_ROWS_I_GE2] += rows_i >= 2, shred_hist[SH_ROWS_IM1_GE2] += rows_im1 >= 2;
+        shred_hist[SH_COLROW_MOD0] += rows % 64 == 0, shred_hist[SH_COLROW_MOD1] += rows % 64 == 1;
+        shred_hist[SH_COLROW_MOD63] += rows % 64 == 63;
+        shred_hist[SH_I_MOD0] += i % 64 == 0, shred_hist[SH_I_MOD1] += i % 64 == 1, shred_hist[SH_I_MOD63] += i % 64 == 63;
+        static const uint32_t ns[8] = {3, 9, 10, 63, 64, 65, 128, 129};
+        for (int x = 0; x < 8; ++x) shred_hist[SH_N3 + x] += n == ns[x];
+    } else {
+        int nobase = 0;
+        for (uint32_t k = 0; k < n; ++k) nobase |= adv[k] == 0;
+        shred_hist[SH_FIN_NOBASE] += nobase;
+        shred_hist[SH_FIN_I_MOD0] += i % 64 == 0, shred_hist[SH_FIN_I_MOD1] += i % 64 == 1;
+        shred_hist[SH_FIN_I_MOD63] += i % 64 == 63;
+    }
+    shred_hist[SH_CCS_CROSS64] += ol % 64 != 0 && (ol + emitted) / 64 > ol / 64;
+    int end_edge = 0, beg_edge = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        uint32_t f = i, l1 = 0;
+        for (uint32_t j = 0; j < g->ncols; ++j)
+            if (g->msacols[(size_t)g->msaidxs[j] * mrow + k + 1] < 4) {
+                if (f == i && j < i) f = j;
+                l1 = j + 1;
+            }
+        if (f >= i) continue;
+        end_edge |= l1 < i && l1 % 64 == 0;
+        beg_edge |= f > 0 && f % 64 == 0;
+    }
+    shred_hist[SH_SPAN_END_EDGE] += end_edge, shred_hist[SH_SPAN_BEG_EDGE] += beg_edge;
+    free(adv);
+}
+
 /* ccs_for (main.c:455-508) and ccs_for2 (main.c:510-647) after ccs_prepare.
  * bplog (optional, shredded mode): per round the pair (breakpoint i,
  * msaidxs->size) that main.c:619-620 prints at -v >= 3, at most bpcap pairs;
@@ -771,8 +870,8 @@ size_t ocsx_zmw_log(opoa_t *g, int mode, const char *seqs, const uint32_t *offs,
     uint8_t *rowcnt = malloc(n ? n : 1);
     uint32_t flag = 1;
     while (flag) {
-        uint32_t i;
-        for (uint32_t ws = initlen;; ws += addlen) {
+        uint32_t i, grow = 0;
+        for (uint32_t ws = initlen;; ws += addlen, ++grow) {
             opoa_beg(g);
             for (i = 0; i < n; ++i)
                 if (pos[i] + ws + minlen >= lens[i]) break;
@@ -781,6 +880,26 @@ size_t ocsx_zmw_log(opoa_t *g, int mode, const char *seqs, const uint32_t *offs,
                 for (i = 0; i < n; ++i) opoa_push(g, seqs + offs[i] + pos[i], lens[i] - pos[i]);
             } else {
                 for (i = 0; i < n; ++i) opoa_push(g, seqs + offs[i] + pos[i], ws);
+            }
+            if (counting) {
+                /* (opoa_shred_hist: the termination test and the pushed lengths) */
+                uint32_t over = 0, first = 0, last = 0, exact = 0, by1 = 0, empty = 0, rmin = UINT32_MAX, rmax = 0;
+                for (uint32_t k = 0; k < n; ++k) {
+                    const uint32_t lim = pos[k] + ws + minlen, rem = lens[k] - pos[k];
+                    if (lim >= lens[k]) ++over, first |= k == 0, last |= k == n - 1;
+                    exact |= lim == lens[k], by1 |= lim + 1 == lens[k], empty |= lens[k] == 0;
+                    rmin = rem < rmin ? rem : rmin, rmax = rem > rmax ? rem : rmax;
+                }
+                if (!flag) {
+                    shred_hist[SH_FIN_NLT3] += n < 3, shred_hist[SH_FIN_EMPTY] += n >= 3 && empty;
+                    shred_hist[SH_FIN_EXACT] += n >= 3 && exact;
+                    shred_hist[SH_FIN_READ0_ONLY] += n >= 3 && over == 1 && first;
+                    shred_hist[SH_FIN_LAST_ONLY] += n >= 3 && over == 1 && last;
+                    shred_hist[SH_FIN_RAGGED] += n >= 3 && rmin <= 1001 && rmin > 0 && rmax >= 5000;
+                    shred_hist[SH_PUSH_GT4096] += rmax > 4096;
+                } else {
+                    shred_hist[SH_NOTFIN_BY1] += by1, shred_hist[SH_PUSH_GT4096] += ws > 4096;
+                }
             }
             opoa_end(g);
             opoa_tidy_msa(g);
@@ -792,11 +911,12 @@ size_t ocsx_zmw_log(opoa_t *g, int mode, const char *seqs, const uint32_t *offs,
             i = 0;
             if (g->ncols > window) {
                 for (i = g->ncols - window; i >= 1; i--) {
-                    uint32_t j, k, nogwin = 0;
+                    uint32_t j, k, nogwin = 0, cmin = UINT32_MAX, coleq = 0;
                     memset(rowcnt, 0, nseq);
                     for (j = i; j < i + window; ++j) {
                         const uint8_t *col = g->msacols + (size_t)g->msaidxs[j] * mrow;
                         if (col[nseq + 1] >= 4) {
+                            if (counting) shred_hist[nogwin ? SH_GAP_SKIP : SH_REJ_LEADGAP]++;
                             if (nogwin) continue;
                             else break;
                         }
@@ -804,15 +924,54 @@ size_t ocsx_zmw_log(opoa_t *g, int mode, const char *seqs, const uint32_t *offs,
                         uint32_t colcnt = 0;
                         for (k = 0; k < nseq; k++)
                             if (col[k + 1] == col[nseq + 1]) colcnt++, rowcnt[k]++;
-                        if (colcnt * 100 < colrate * nseq) break;
+                        if (colcnt * 100 < colrate * nseq) {
+                            if (counting) {
+                                shred_hist[SH_REJ_COL_OFF0 + (j - i)]++;
+                                shred_hist[SH_REJ_COL_BY1] += (colcnt + 1) * 100 >= colrate * nseq;
+                                shred_hist[SH_REJ_N10_C6] += nseq == 10 && colcnt == 6;
+                                shred_hist[SH_REJ_N10_C7] += nseq == 10 && colcnt == 7;
+                            }
+                            break;
+                        }
+                        cmin = colcnt < cmin ? colcnt : cmin, coleq |= colcnt * 100 == colrate * nseq;
                     }
+                    if (counting && j >= i + window && nogwin < minwin) shred_hist[SH_REJ_NOG_LT5]++;
                     if (j < i + window || nogwin < minwin) continue;
                     for (k = 0; k < nseq; ++k)
                         if (rowcnt[k] * 100 < rowrate * nogwin) break;
-                    if (k >= nseq) break;
+                    if (counting && k < nseq) shred_hist[SH_REJ_ROW_BY1] += (rowcnt[k] + 1u) * 100 >= rowrate * nogwin;
+                    if (k >= nseq) {
+                        if (counting) {
+                            uint32_t rmin = UINT32_MAX;
+                            for (k = 0; k < nseq; ++k) rmin = rowcnt[k] < rmin ? rowcnt[k] : rmin;
+                            shred_hist[nogwin == 5 ? SH_ACC_NOG5 : nogwin == 10 ? SH_ACC_NOG10 : SH_ACC_NOG6_9]++;
+                            shred_hist[SH_ACC_COL_EQ_N5] += coleq && nseq == 5, shred_hist[SH_ACC_COL_EQ_N10] += coleq && nseq == 10;
+                            shred_hist[SH_ACC_N9_C6] += nseq == 9 && cmin == 6, shred_hist[SH_ACC_N9_C7] += nseq == 9 && cmin == 7;
+                            shred_hist[SH_ACC_ROW_EQ_NOG5] += nogwin == 5 && rmin * 100 == rowrate * nogwin;
+                            shred_hist[SH_ACC_ROW_EQ_NOG10] += nogwin == 10 && rmin * 100 == rowrate * nogwin;
+                        }
+                        break;
+                    }
+                }
+            }
+            if (counting) {
+                if (i >= 1) {
+                    const uint32_t d = g->ncols - window - i;
+                    shred_hist[d == 0 ? SH_D0 : d <= 62 ? SH_D1_62 : d == 63 ? SH_D63 : d == 64 ? SH_D64 : d == 65 ? SH_D65
+                               : d <= 126 ? SH_D66_126 : d == 127 ? SH_D127 : d == 128 ? SH_D128 : SH_D_GE129]++;
+                    shred_hist[SH_D_GT1000] += d > 1000, shred_hist[SH_I_LE16] += i <= 16;
+                    shred_hist[SH_I_1] += i == 1, shred_hist[SH_I_2] += i == 2;
+                } else {
+                    shred_hist[SH_NONE_MULT64] += g->ncols > window && (g->ncols - window) % 64 == 0;
+                    shred_hist[SH_NONE_LT64] += g->ncols < window + 64;
                 }
             }
             if (i >= 1) break;
+        }
+        if (counting) {
+            shred_hist[grow == 0 ? SH_GROW_0 : grow == 1 ? SH_GROW_1 : grow == 2 ? SH_GROW_2 : SH_GROW_GE3]++;
+            shred_hist[flag ? SH_GROW_FOUND : SH_GROW_FINAL] += grow >= 1;
+            count_shred_emit(g, n, i, !flag, ol, pos, lens);
         }
         /* main.c:619-620 (-v >= 3) */
         if (bplog && nround < bpcap) bplog[2 * nround] = i, bplog[2 * nround + 1] = g->ncols;
@@ -826,6 +985,7 @@ size_t ocsx_zmw_log(opoa_t *g, int mode, const char *seqs, const uint32_t *offs,
             if (col[nseq + 1] < 4) out[ol++] = BIT_BASE[col[nseq + 1]];
         }
     }
+    if (counting) shred_hist[nround == 1 ? SH_ROUNDS_1 : nround == 2 ? SH_ROUNDS_2 : nround <= 5 ? SH_ROUNDS_3_5 : SH_ROUNDS_GE6]++;
     free(pos);
     free(rowcnt);
     out[ol] = 0;

@@ -288,7 +288,10 @@ def test_read_beyond_lds_buffer(engine, mode):
     """Segments of 110 kb (more than the LDS read buffer's 100 kb): the slice
     runs the HBM-read kernel instance, in the same call as ordinary ZMWs."""
     zs = [synth(7300, 110_000, 5), synth(7301, 3000, 6), synth(7302, 40_000, 5)]
+    before = engine.hbm_launches()
     _check(engine, zs, mode)
+    # (a tight-cap shredded slice pushes windows, not segments: it stays on the LDS instance)
+    assert engine.hbm_launches() - before >= (1 if mode == cx.MODE_PRIMITIVE else 0)
 
 
 def test_more_segments_than_lds_cursors(engine):
@@ -302,7 +305,9 @@ def test_more_segments_than_lds_cursors(engine):
         s = bytearray(ins)
         s[rnd.randrange(60)] = rnd.choice(b"ACGT")
         segs.append(bytes(s))
+    before = engine.hbm_launches()
     _check(engine, [raw(segs), synth(7400, 2000, 6)], cx.MODE_SHRED)
+    assert engine.hbm_launches() - before >= 1
 
 
 @pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5])

@@ -102,7 +102,9 @@ def test_hbm_read_instance(pengine):
         s = bytearray(ins)
         s[rnd.randrange(60)] = rnd.choice(b"ACGT")
         segs.append(bytes(s))
+    before = pengine.hbm_launches()
     _check(pengine, [raw(segs)], cx.MODE_SHRED)
+    assert pengine.hbm_launches() - before >= 1
 
 
 @pytest.mark.parametrize("hook", ["tight_out", "tight_rows"])

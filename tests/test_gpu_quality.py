@@ -98,7 +98,9 @@ def test_hbm_read_instance(qengine):
         s = bytearray(ins)
         s[rnd.randrange(60)] = rnd.choice(b"ACGT")
         segs.append(bytes(s))
+    before = qengine.hbm_launches()
     _check(qengine, [raw(segs)], cx.MODE_SHRED)
+    assert qengine.hbm_launches() - before >= 1
 
 
 @pytest.mark.parametrize("hook", ["tight_out", "tight_rows"])

@@ -263,6 +263,154 @@ def tie_cases() -> dict[str, list[bytes]]:
     return cases
 
 
+# ---------------------------------------------------------------------------
+# Constructed cases for the shredding loop around the POA call (SPEC.md §7:
+# the breakpoint scan, the window growth, the cursors, the emission over
+# several rounds).  tests/test_shred_cases.py states which class each case
+# must reach, from the oracle's opoa_shred_hist; tests/test_gpu_shred.py
+# compares every kernel object with the oracle on them.  Exact reads again.
+# Three constructions:
+#   copies     n exact copies of T[:L], with single substituted bases: an
+#              isolated substitution stays a mismatch (X = -6 against two gaps,
+#              2 (O + E) = -10), so column c of the first 2,000-base window is
+#              T's base c and the number of reads carrying it is chosen freely.
+#              A "dirty" column (n = 5: two reads keep the base, two carry a
+#              second, one a third; 2 * 100 < 60 * 5) rejects every candidate
+#              window that holds it; dirty columns every 9 bases from c to the
+#              window's end make c - 10 the first accepted candidate, at depth
+#              (ncols - 10) - i = 2000 - c.
+#   zone       reads 0 and 1 carry a random string over {A, C}, read 2 one
+#              over {G, T}: nothing aligns, read 2's bases are gap-consensus
+#              columns, the others' base columns read 2 never matches.  After a
+#              shared prefix of p bases the scan accepts i = p - 5 (five base
+#              columns, then five skipped gap columns).
+#   lengths    which read makes a round final, and when.
+# ---------------------------------------------------------------------------
+SHRED_DEPTHS = (63, 64, 65, 100, 127, 128, 129)
+SHRED_NS = (63, 64, 65, 128, 129)
+
+
+def _other(b: int, j: int = 1) -> int:
+    return b"ACGT"[(b"ACGT".index(b) + j) % 4]
+
+
+def _copies(T: bytes, n: int, L: int, subs=(), dirty=()) -> list[bytes]:
+    """n copies of T[:L]; subs: (read, column, j) substitutes T's base by the
+    j-th next letter; dirty: columns made dirty (n = 5, see above)."""
+    reads = [bytearray(T[:L]) for _ in range(n)]
+    subs = list(subs) + [(k, c, j) for c in dirty for k, j in ((2, 1), (3, 1), (4, 2))]
+    for k, c, j in subs:
+        reads[k][c] = _other(T[c], j)
+    return [bytes(r) for r in reads]
+
+
+def _dirty_from(c: int) -> list[int]:
+    """Dirty columns from c to the end of the first 2,000-base window, at most
+    9 apart, the last one in 1990 .. 1995 (no candidate window above c - 10 is
+    clean, none of them at the window's last bases)."""
+    cols = list(range(c, 1996, 9))
+    return cols if cols[-1] >= 1990 else cols + [1992]
+
+
+def shred_cases() -> dict[str, list[bytes]]:
+    rng = random.Random(7000)
+    T = _rb(rng, 14000)
+    L = 4200  # two rounds: 2,000 bases pushed, then the final push
+    cases = {}
+    # ---- lengths: rounds and termination
+    cases["copies_3000"] = [T[:3000]] * 3          # pos + 2000 + 1000 == len: one final round
+    cases["copies_3001"] = [T[:3001]] * 3          # one base longer: (1990, 2000) then the final round
+    cases["copies_4990"] = [T[:4990]] * 3          # the first breakpoint leaves every cursor at len - 3000
+    cases["copies_14000"] = [T[:14000]] * 3        # seven rounds
+    for Lf in (2943, 2944, 2945):                  # final rounds of 64 m - 1, 64 m, 64 m + 1 columns
+        cases[f"final_{Lf}"] = [T[:Lf]] * 3
+    cases["two_reads"] = [T[:5000]] * 2
+    cases["empty_segment"] = [T[:5000], b"", T[:5000], T[:5000]]
+    cases["read0_short"] = [T[:3000], T[:4000], T[:4000]]
+    cases["last_short"] = [T[:4000], T[:4000], T[:3000]]
+    cases["ragged_1001"] = [T[:5000], T[:5200], T[:1001]]
+    cases["span_end_edge"] = [T[:3000], T[:3000], T[:2944]]   # read 2's span ends at column 46 * 64
+    cases["span_begin_edge"] = [T[:3000], T[:3000], T[64:3000]]  # ... begins at column 64
+    # ---- zone: depths by the zone's length, small i, growth
+    for k in (34, 35, 66):                         # depth 2 k - 5 = 63, 65, 127
+        A, B, p, s = _rb2(rng, k, b"AC"), _rb2(rng, k, b"GT"), T[:2000 - k], T[2000:5200]
+        cases[f"zone_{k}"] = [p + A + s, p + A + s, p + B + s]
+    s = T[2000:6000]
+    for pre in (6, 7, 10, 20):                     # i = pre - 5
+        A, B = _rb2(rng, 2000 - pre, b"AC"), _rb2(rng, 2000 - pre, b"GT")
+        cases[f"prefix_{pre}"] = [T[:pre] + A + s, T[:pre] + A + s, T[:pre] + B + s]
+    A, B = _rb2(rng, 1990, b"AC"), _rb2(rng, 1990, b"GT")
+    cases["prefix_10_read2_from_5"] = [T[:10] + A + s, T[:10] + A + s, T[5:10] + B + s]  # i = 5: no base of read 2 before it
+    A, B, s = _rb2(rng, 2000, b"AC"), _rb2(rng, 2000, b"GT"), T[2000:8000]
+    cases["dirty_2000_then_shared"] = [A + s, A + s, B + s]   # grows to 4,000, then finds a breakpoint
+    for Ld in (3100, 5100, 7100):                  # 1, 2, 3 growths, then the final push
+        A, B = _rb2(rng, Ld, b"AC"), _rb2(rng, Ld, b"GT")
+        cases[f"dirty_{Ld}"] = [A, A, B]
+    # read 1 lacks 44 single bases of the first window: its 2,000 bases reach
+    # further into A, the MSA has 4,042 columns: ncols - 10 = 63 * 64, nothing found
+    A, B = _rb2(rng, 3200, b"AC"), _rb2(rng, 3100, b"GT")
+    a1 = bytearray(A)
+    for x in range(44):
+        del a1[1993 - 40 * x]
+    cases["dirty_4042_columns"] = [A, bytes(a1), B]
+    # ---- copies: the scan's steps of 64 candidates, bp_ok's thresholds
+    for d in SHRED_DEPTHS:
+        cases[f"depth_{d}"] = _copies(T, 5, L, dirty=_dirty_from(2000 - d))
+    for c in (1993, 1994, 1995):                   # i = c - 10 = 1983, 1984 = 31 * 64, 1985
+        cases[f"i_mod64_{(c - 10) % 64}"] = _copies(T, 5, L, dirty=[c])
+    cases["col_n5_below"] = _copies(T, 5, L, dirty=[1990])    # 2 of 5: offsets 0 .. 9 of candidates 1990 .. 1981
+    cases["col_n5_equal"] = _copies(T, 5, L, [(3, 1995, 1), (4, 1995, 1)])      # 3 of 5 at 60 %
+    cases["col_n10_equal"] = _copies(T, 10, L, [(8, 1995, 1), (9, 1995, 1)])    # 8 of 10 at 80 %
+    for n, c in ((9, 7), (10, 7), (9, 6), (10, 6)):           # 7 and 6 reads agree: 60 % of 9, not 80 % of 10
+        cases[f"col_n{n}_c{c}"] = _copies(T, n, L, [(k, 1995, 1) for k in range(c, n)])
+    # read 4 mismatches at 3 of the top window's 10 columns (7 < 8), then at 2 of candidate 1987's
+    cases["row_below_then_equal"] = _copies(T, 5, L, [(4, 1991, 1), (4, 1994, 1), (4, 1997, 1)])
+    cases["rows_at_i"] = _copies(T, 5, L, [(4, 1990, 1), (3, 1989, 1)])         # two rows in columns i and i - 1
+    for g in (1, 2, 3, 4):
+        # g bases inserted in read 1 six columns under a dirty column: the
+        # first clean candidate's window holds g gap columns, nogwin = 10 - g
+        # (g = 4: candidate 1950 is clean but for its leading gap column)
+        reads = _copies(T, 5, L, dirty=_dirty_from(1956))
+        ins = bytes(_other(T[1950], 1 + x % 2) for x in range(g))
+        reads[1] = reads[1][:1950] + ins + reads[1][1950:]
+        cases[f"nogwin_{10 - g}"] = reads
+    # ---- cursors: an insertion in one read and a deletion in another before the breakpoint
+    cases["indel"] = [T[:L], T[:500] + b"GAT" + T[500:L], T[:900] + T[904:L]]
+    for n in SHRED_NS:
+        # read counts around the 64-read mask words; the reads at the words'
+        # edges carry an insertion, the last one a deletion
+        reads = [T[:3001]] * n
+        for k in {0, 62, 63, 64, 127, 128} & set(range(n - 1)):
+            reads[k] = T[:700] + bytes([_other(T[700]), _other(T[700], 2)]) + T[700:3001]
+        reads[n - 1] = T[:1200] + T[1203:3004]
+        cases[f"n{n}"] = reads
+    return cases
+
+
+def _rb2(rng: random.Random, n: int, letters: bytes) -> bytes:
+    return bytes(rng.choice(letters) for _ in range(n))
+
+
+def shred_golden_entry(poa, reads: list[bytes]) -> dict:
+    """What tests/golden/shred_cases.json keeps per case (tools/make_golden.py):
+    the SHA-256 of the oracle's shredded CCS and its whole breakpoint log."""
+    import hashlib
+    z = raw(reads)
+    ccs, log = poa.zmw_breakpoints(z.seqs, z.offs, z.lens)
+    return {"sha256": hashlib.sha256(ccs).hexdigest(), "len": len(ccs), "log": [[int(a), int(b)] for a, b in log]}
+
+
+def hbm_cursor_zmw(seed: int = 7100):
+    """3 reads: a 4,100-base disjoint-alphabet zone (two growths: the pushed
+    6,000-base window exceeds the tight read cap), then 3 exact copies of a
+    100,200-base random string (segments beyond the LDS read buffer: the re-run
+    with full caps takes the HBM-read instance, whose cursors then advance over
+    about 55 rounds)."""
+    rng = random.Random(seed)
+    A, B, S = _rb2(rng, 4100, b"AC"), _rb2(rng, 4100, b"GT"), _rb(rng, 100200)
+    return [A + S, A + S, B + S]
+
+
 RECORD_FAMILIES = {"ladder": ladder_cases, "block_edge": block_edge_cases, "band": band_cases, "tie": tie_cases}
 
 
