@@ -196,6 +196,39 @@ struct PassSet {
     }
 };
 
+// The gathered subread-to-CCS maps (SPEC.md §11) of one ccsx_gpu_run call or
+// one collected batch, per ZMW of the call in input order
+struct MapSet {
+    std::vector<uint32_t> words;   // a word per pushed base, a ZMW's segments back to back
+    std::vector<uint64_t> spos;    // per gathered segment: word offset into words
+    std::vector<uint32_t> slen;    // per gathered segment: entries
+    std::vector<uint64_t> seg0;    // per ZMW: its first segment in spos / slen
+    std::vector<uint32_t> nseg;    // per ZMW: segments
+    std::vector<uint8_t> ok;       // per ZMW: it has a result (status 0)
+    void reset(size_t nz)
+    {
+        words.clear();
+        spos.clear();
+        slen.clear();
+        seg0.assign(nz, 0);
+        nseg.assign(nz, 0);
+        ok.assign(nz, 0);
+    }
+    void put(size_t g, const uint32_t *map, const uint32_t *len, uint32_t n)
+    {
+        seg0[g] = spos.size();
+        nseg[g] = n;
+        ok[g] = 1;
+        uint64_t tot = 0;
+        for (uint32_t k = 0; k < n; ++k) {
+            spos.push_back(words.size() + tot);
+            slen.push_back(len[k]);
+            tot += len[k];
+        }
+        words.insert(words.end(), map, map + tot);
+    }
+};
+
 // One staged slice and everything it owns on the device and the host.  A
 // context has two: ccsx_gpu_run stages and launches slice k + 1 on the other
 // slot's stream while slice k's kernel runs, so one slice's tail (the launch
@@ -223,10 +256,21 @@ struct Slot {
     {
         return reinterpret_cast<const uint32_t *>(h_out.p + pst_off()) + size_t(desc[zmw].seg0) * ccsx::kPassWords;
     }
+    // staged with the subread-to-CCS map (ccsx_gpu_set_base_map): a word per
+    // pushed base in d_bmap, ZMW i's segments back to back at word hbmoff[i]
+    // (d_bmoff; its 8 bytes per ZMW lie within the 32 that every size counts
+    // for a ZMW's tables); in h_out at bm_off(), behind the pass records
+    bool bmap = false;
+    uint64_t nbase_total = 0;          // pushed bases of the slice
+    uint64_t bm_off() const { return ((pstat ? pst_off() + pst_bytes() : out_bytes * (qual ? 2 : 1)) + 7) & ~uint64_t(7); }
+    uint64_t bm_bytes() const { return bmap ? nbase_total * 4 : 0; }
+    const uint32_t *h_bmap(size_t zmw) const { return reinterpret_cast<const uint32_t *>(h_out.p + bm_off()) + hbmoff[zmw]; }
+    std::vector<uint64_t> hbmoff;
     std::vector<ccsx::ZmwDesc> desc;
     std::vector<uint32_t> hoff, hlen, order;  // host copies the async H2D reads from
     DevBuf d_prof, d_bp;
     DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells, d_pstat;
+    DevBuf d_bmap, d_bmoff;
     HostBuf h_out, h_seq;
     std::vector<uint32_t> h_olen, h_ncols, h_bp;
     std::vector<int32_t> h_status;
@@ -235,7 +279,7 @@ struct Slot {
     void release()
     {
         DevBuf *bufs[] = {&d_bp, &d_prof, &d_seq, &d_soff, &d_slen, &d_desc, &d_order, &d_ws, &d_out,
-                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_pstat};
+                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_pstat, &d_bmap, &d_bmoff};
         for (DevBuf *b : bufs) b->release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -294,6 +338,10 @@ struct ccsx_ctx {
     // ccsx_gpu_pass_stats(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
     int last_pst = 0;
     PassSet run_pst;                   // ccsx_gpu_run's gathered pass records
+    bool base_map = false;             // stage the subread-to-CCS map beside the CCS (ccsx_gpu_set_base_map)
+    // ccsx_gpu_base_map(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
+    int last_bm = 0;
+    MapSet run_bm;                     // ccsx_gpu_run's gathered maps
     std::vector<uint32_t> run_bp;      // ccsx_gpu_run: the gathered logs, (i, ncols) pairs
     std::vector<uint64_t> run_bp_off;  // per ZMW of the call: offset into run_bp (pairs)
     std::vector<uint32_t> run_bp_n;    // per ZMW of the call: rounds
@@ -314,6 +362,9 @@ struct ccsx_ctx {
         bool pstat = false;            // submitted with pass statistics on
         bool has_pst = false;          // collected, and pst holds its pass records
         PassSet pst;
+        bool bmap = false;             // submitted with the subread-to-CCS map on
+        bool has_bm = false;           // collected, and bm holds its maps
+        MapSet bm;
     } tk[2];
 };
 
@@ -465,7 +516,8 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::ZLayout L;
     ccsx::zlayout(L, d);
     return ccsx::align256(L.total) + hi + d.outcap + (c->quality ? d.outcap : 0u) + uint64_t(zi.nseg) * 8 +
-           (c->pass_stats ? uint64_t(zi.nseg) * ccsx::kPassWords * 4 : 0u) + sizeof(ccsx::ZmwDesc) + 32;
+           (c->pass_stats ? uint64_t(zi.nseg) * ccsx::kPassWords * 4 : 0u) + (c->base_map ? S * 4 : 0u) +
+           sizeof(ccsx::ZmwDesc) + 32;
 }
 
 // The bytes a slice staged into slot s may need now: the device's free memory
@@ -478,7 +530,7 @@ static int slot_avail(ccsx_ctx *c, const Slot &s, uint64_t &avail)
 {
     size_t freeb = 0, totb = 0;
     HIPCHK(c, hipMemGetInfo(&freeb, &totb));
-    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap + s.d_pstat.cap;
+    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap + s.d_pstat.cap + s.d_bmap.cap;
     avail = have > (1ull << 30) ? have - (1ull << 30) : 0;
     return 0;
 }
@@ -517,8 +569,10 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, hipSetDevice(c->device));
     s.nz = nz;
     s.desc.assign(nz, ccsx::ZmwDesc{});
-    uint64_t seq_b = 0, ws_b = 0, out_b = 0, msa_b = 0, bp_w = 0;
+    uint64_t seq_b = 0, ws_b = 0, out_b = 0, msa_b = 0, bp_w = 0, nbase = 0;
     uint32_t nseg = 0, lmax_all = 0, nmax = 0;
+    s.bmap = c->base_map && !with_msa;
+    s.hbmoff.resize(s.bmap ? nz : 0);
     for (size_t i = 0; i < nz; ++i) {
         const ccsx_zmw_in &zi = z[i];
         uint64_t S, hi;
@@ -549,10 +603,13 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         d.bpcap = c->bp_log ? (full_caps ? uint32_t(S + 2) : uint32_t(S / 512 + 64)) : 0u;
         d.bp_off = bp_w;
         bp_w += c->bp_log ? 1 + 2 * uint64_t(d.bpcap) : 0;
+        if (s.bmap) s.hbmoff[i] = nbase;
+        nbase += S;
         nseg += zi.nseg;
         lmax_all = std::max(lmax_all, lmax);
         nmax = std::max(nmax, zi.nseg);
     }
+    s.nbase_total = nbase;
     s.seq_bytes = seq_b, s.ws_bytes = ws_b, s.out_bytes = out_b, s.msa_bytes = msa_b;
     s.bp_words = bp_w;
     s.nseg_total = nseg;
@@ -560,6 +617,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     const uint64_t qual_b = s.qual ? out_b : 0;
     s.pstat = c->pass_stats && !with_msa;
     const uint64_t pst_b = s.pst_bytes();
+    const uint64_t bm_b = s.bm_bytes();
     // 2-bit read buffer (ccsx_kernel.hip stage_read); at least one band:
     // every lane reads its window bytes even when the read is shorter.  A
     // slice with a read or a cursor array beyond the LDS budget runs the
@@ -615,7 +673,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + qual_b + pst_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
+    const uint64_t need = seq_b + ws_b + out_b + qual_b + pst_b + bm_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 +
+                          nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
         // already cut the slice to what is free; a submitted batch cannot be cut)
@@ -643,6 +702,10 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, s.d_ws.reserve(ws_b));
     HIPCHK(c, s.d_out.reserve(out_b + qual_b));
     if (pst_b) HIPCHK(c, s.d_pstat.reserve(pst_b));
+    if (s.bmap) {
+        HIPCHK(c, s.d_bmap.reserve(bm_b));
+        HIPCHK(c, s.d_bmoff.reserve(nz * 8));
+    }
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
     HIPCHK(c, s.d_ncols.reserve(nz * 4));
@@ -729,6 +792,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, hipMemcpyAsync(s.d_soff.p, s.hoff.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_slen.p, s.hlen.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_desc.p, s.desc.data(), nz * sizeof(ccsx::ZmwDesc), hipMemcpyHostToDevice, s.stream));
+    if (s.bmap && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
     // launch order: decreasing estimated POA work (ccsx_zmw_cost: S x (28 +
     // n)), ties in input order -- longest-processing-time first, so a launch
     // ends on its cheapest ZMWs
@@ -770,6 +834,9 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     a.bplog = s.bp_words ? s.d_bp.as<uint32_t>() : nullptr;
     a.qual = s.qual ? s.d_out.as<uint8_t>() + s.out_bytes : nullptr;
     a.pstat = s.pst_bytes() ? s.d_pstat.as<uint32_t>() : nullptr;
+    // (a slice without a pushed base has no map to write: the feature-off kernels run it)
+    a.bmap = s.bm_bytes() ? s.d_bmap.as<uint32_t>() : nullptr;
+    a.bmoff = s.bm_bytes() ? s.d_bmoff.as<uint64_t>() : nullptr;
     if (c->profiling) {
         HIPCHK(c, s.d_prof.reserve(s.nz * ccsx::kProfSlots * 8));
         a.prof = s.d_prof.as<unsigned long long>();
@@ -795,7 +862,10 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
     const size_t nz = s.nz;
     const uint64_t planes = s.qual ? 2 : 1;  // the quality plane follows the CCS plane, one copy for both
     // (the pass records follow the planes, 8-byte aligned)
-    HIPCHK(c, s.h_out.reserve(s.pstat ? s.pst_off() + s.pst_bytes() : s.out_bytes * planes,
+    // (and the map follows those, 8-byte aligned)
+    HIPCHK(c, s.h_out.reserve(s.bmap    ? s.bm_off() + s.bm_bytes()
+                              : s.pstat ? s.pst_off() + s.pst_bytes()
+                                        : s.out_bytes * planes,
                               c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
     s.h_olen.resize(nz);
     s.h_status.resize(nz);
@@ -808,6 +878,8 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
         HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes * planes, hipMemcpyDeviceToHost, s.stream));
         if (s.pst_bytes())
             HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pst_off(), s.d_pstat.p, s.pst_bytes(), hipMemcpyDeviceToHost, s.stream));
+        if (s.bm_bytes())
+            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.bm_off(), s.d_bmap.p, s.bm_bytes(), hipMemcpyDeviceToHost, s.stream));
         if (s.bp_words)
             HIPCHK(c, hipMemcpyAsync(s.h_bp.data(), s.d_bp.p, s.bp_words * 4, hipMemcpyDeviceToHost, s.stream));
     }
@@ -844,6 +916,7 @@ int ccsx_gpu_stage_ex(ccsx_ctx *c, const ccsx_zmw_in *z, size_t nz, int with_msa
     }
     c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
     c->last_pst = 0;
+    c->last_bm = 0;
     const int r = stage_slot(c, s, z, nz, with_msa, full_caps);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(s.stream));
@@ -896,8 +969,9 @@ int ccsx_gpu_fetch(ccsx_ctx *c, ccsx_zmw_out *out)
     if (!c) return -1;
     c->last_qual = 0;
     c->last_pst = 0;
+    c->last_bm = 0;
     const int r = fetch_slot(c, c->slot[0], out);
-    if (r == 0 || r == -2) c->last_qual = c->last_pst = 2;
+    if (r == 0 || r == -2) c->last_qual = c->last_pst = c->last_bm = 2;
     return r;
 }
 
@@ -991,6 +1065,8 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     c->run_qlen.assign(c->quality ? nz : 0, 0);
     c->last_pst = 0;
     c->run_pst.reset(c->pass_stats ? nz : 0);
+    c->last_bm = 0;
+    c->run_bm.reset(c->base_map ? nz : 0);
     c->run_bp.clear();
     c->run_bp_off.assign(nz, 0);
     c->run_bp_n.assign(nz, 0);
@@ -1053,6 +1129,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
                 c->run_qual.insert(c->run_qual.end(), q, q + o[i].len);
             }
             if (s.pstat) c->run_pst.put(g, s.h_pstat(i), s.desc[i].n);
+            if (s.bmap) c->run_bm.put(g, s.h_bmap(i), s.hlen.data() + s.desc[i].seg0, s.desc[i].n);
             if (s.bp_words && mode == CCSX_MODE_SHRED) {
                 const uint32_t *lg = s.h_bp.data() + s.desc[i].bp_off;
                 c->run_bp_off[g] = c->run_bp.size() / 2;
@@ -1203,12 +1280,14 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
         out[c->fault].len = 0;
         if (c->quality) c->run_qlen[c->fault] = 0;
         if (c->pass_stats) c->run_pst.ok[c->fault] = 0;
+        if (c->base_map) c->run_bm.ok[c->fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     c->fault = -1;
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(c->run_arena.data() + aoff[i]);
     if (c->quality) c->last_qual = 1;
     if (c->pass_stats) c->last_pst = 1;
+    if (c->base_map) c->last_bm = 1;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1287,6 +1366,7 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     }
     if (si == 0 && c->last_qual == 2) c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
     if (si == 0 && c->last_pst == 2) c->last_pst = 0;
+    if (si == 0 && c->last_bm == 2) c->last_bm = 0;
     r = stage_slot(c, s, z, nz, 0, 0);
     if (!r) r = launch_slot(c, s, mode);
     c->shred_caps = false;
@@ -1301,6 +1381,8 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     c->tk[si].has_qual = false;
     c->tk[si].pstat = s.pstat;
     c->tk[si].has_pst = false;
+    c->tk[si].bmap = s.bmap;
+    c->tk[si].has_bm = false;
     c->fault = -1;
     *slot = si;
     return 0;
@@ -1345,6 +1427,14 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         PassStats(ccsx_ctx *x, bool on) : c(x), was(x->pass_stats) { c->pass_stats = on; }
         ~PassStats() { c->pass_stats = was; }
     } pass_stats(c, t.pstat);
+    t.has_bm = false;
+    t.bm.reset(t.bmap ? nz : 0);
+    struct BaseMap {
+        ccsx_ctx *c;
+        bool was;
+        BaseMap(ccsx_ctx *x, bool on) : c(x), was(x->base_map) { c->base_map = on; }
+        ~BaseMap() { c->base_map = was; }
+    } base_map(c, t.bmap);
     auto gather = [&](const ccsx_zmw_out *res, const uint32_t *idx, size_t n, bool can_retry) {
         size_t add = 0;
         for (size_t i = 0; i < n; ++i) add += res[i].status ? 0 : res[i].len;
@@ -1378,6 +1468,7 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
             }
             // (gather's results are the slot's, in its order: ZMW i of the slot)
             if (s.pstat) t.pst.put(g, s.h_pstat(i), s.desc[i].n);
+            if (s.bmap) t.bm.put(g, s.h_bmap(i), s.hlen.data() + s.desc[i].seg0, s.desc[i].n);
         }
     };
     gather(o.data(), nullptr, nz, true);
@@ -1422,11 +1513,13 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         out[t.fault].len = 0;
         if (t.qual) t.qlen[t.fault] = 0;
         if (t.pstat) t.pst.ok[t.fault] = 0;
+        if (t.bmap) t.bm.ok[t.fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(t.arena.data() + aoff[i]);
     t.has_qual = t.qual;
     t.has_pst = t.pstat;
+    t.has_bm = t.bmap;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1670,6 +1763,79 @@ int ccsx_gpu_pass_stats(ccsx_ctx *c, int slot, size_t zmw, const ccsx_pass_stat 
     return 0;
 }
 
+int ccsx_gpu_set_base_map(ccsx_ctx *c, int on)
+{
+    if (!c) return -1;
+    c->base_map = on != 0;
+    return 0;
+}
+
+int ccsx_gpu_base_map(ccsx_ctx *c, int slot, size_t zmw, uint32_t seg, const uint32_t **map, uint32_t *len)
+{
+    if (!c || !map || !len) return -1;
+    *map = nullptr;
+    *len = 0;
+    if (slot < -1 || slot > 1) {
+        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
+        return -1;
+    }
+    const char *off = "that batch ran with the base map off (ccsx_gpu_set_base_map)";
+    const char *range = "ZMW index beyond the batch";
+    const char *srange = "segment index beyond the ZMW's segments";
+    const char *failed = "that ZMW failed: it has no base map";
+    const MapSet *ms = nullptr;
+    if (slot >= 0) {
+        const auto &t = c->tk[slot];
+        if (t.pending || !t.has_bm) {
+            c->err = t.pending ? "that slot's batch is not collected yet" : off;
+            return -1;
+        }
+        ms = &t.bm;
+    } else if (c->last_bm == 1) {
+        ms = &c->run_bm;
+    }
+    if (ms) {
+        if (zmw >= ms->nseg.size()) {
+            c->err = range;
+            return -1;
+        }
+        if (!ms->ok[zmw]) {
+            c->err = failed;
+            return -1;
+        }
+        if (seg >= ms->nseg[zmw]) {
+            c->err = srange;
+            return -1;
+        }
+        *map = ms->words.data() + ms->spos[ms->seg0[zmw] + seg];
+        *len = ms->slen[ms->seg0[zmw] + seg];
+        return 0;
+    }
+    const Slot &s = c->slot[0];
+    if (c->last_bm != 2 || !s.bmap) {
+        c->err = off;
+        return -1;
+    }
+    if (zmw >= s.nz) {
+        c->err = range;
+        return -1;
+    }
+    if (s.h_status[zmw]) {
+        c->err = failed;
+        return -1;
+    }
+    if (seg >= s.desc[zmw].n) {
+        c->err = srange;
+        return -1;
+    }
+    const uint32_t *ln = s.hlen.data() + s.desc[zmw].seg0;
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < seg; ++k) at += ln[k];
+    *map = s.h_bmap(zmw) + at;
+    *len = ln[seg];
+    return 0;
+}
+
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -1720,7 +1886,7 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.pst_bytes() + s.msa_bytes;
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.pst_bytes() + s.bm_bytes() + s.msa_bytes;
 }
 
 // single-POA path used by the bspoa-compatible API (bspoa_gpu.cpp)

@@ -3168,15 +3168,88 @@ __device__ __forceinline__ void pass_stats(const Z &z, uint32_t i, uint32_t n, u
     }
 }
 
+// inclusive prefix sum over the wave's lanes
+__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v)
+{
+    const uint32_t lane = lane_id();
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, d);
+        v += lane >= d ? u : 0u;
+    }
+    return v;
+}
+
+// SPEC.md §11: the map entries of the read bases in the emitted columns [0, i)
+// of this POA call, into the ZMW's map bm (KArgs::bmap at KArgs::bmoff[zmw]:
+// the segments' entries back to back in push order); ol = the CCS bases emitted
+// before this call; pos0 = the reads' cursors at the start of the round (null:
+// 0, the -P call).  pass_stats' walk: per 64 reads (mask word w, lane = read,
+// which carries the entry its read's next base takes) the wave goes over the
+// columns 64 at a time (lane = column: t = its CCS offset from the ballot of
+// the base columns); per read bit the lanes whose column holds a base of the
+// read store their words at consecutive entries (a read's bases lie in
+// increasing columns), the ballot's popcount advances the read.  Every entry is
+// written once per launch; a store beyond the segment's entries (an MSA that
+// broke §10's first invariant) is dropped.
+__device__ __forceinline__ void base_map(const Z &z, uint32_t i, uint32_t n, uint32_t ol, const uint32_t *slen,
+                                         const uint32_t *pos0, uint32_t *bm)
+{
+    const uint32_t lane = lane_id(), nw = z.d.nw;
+    const uint64_t *mem = G_mem(z, z.cur);
+    if (i == 0) return;
+    uint32_t seg = 0;  // entries of the segments before mask word w's
+    for (uint32_t w = 0; w * 64 < n; ++w) {
+        const uint32_t k = w * 64 + lane;
+        const uint32_t kn = n - w * 64 < 64 ? n - w * 64 : 64;
+        const uint32_t ln = k < n ? slen[k] : 0u;
+        const uint32_t end = seg + wave_incl_add(ln);  // one past read k's entries
+        uint32_t cur = end - ln + (pos0 && k < n ? pos0[k] : 0u);
+        seg = (uint32_t)__builtin_amdgcn_readlane((int)end, 63);
+        uint32_t base = 0;  // base columns before c0
+        PsCols x0 = ps_cols(z, lane, i, w), x1 = ps_cols(z, 64 + lane, i, w);
+        uint64_t h = ps_rows(mem, x0.ra, x0.re, nw, w);
+        for (uint32_t c0 = 0; c0 < i; c0 += 64) {
+            const PsCols x2 = ps_cols(z, c0 + 128 + lane, i, w);
+            const uint64_t h1 = ps_rows(mem, x1.ra, x1.re, nw, w);
+            const uint64_t bb = ballot(x0.cb < 4);
+            const uint32_t t = ol + base + lanes_below(bb);
+            // (32 read bits at a time: the tests stay 32-bit)
+            for (uint32_t k0 = 0; k0 < kn; k0 += 32) {
+                const uint32_t hx = (uint32_t)(h >> k0), mx = (uint32_t)(x0.m >> k0);
+                const uint32_t cnt = kn - k0 < 32 ? kn - k0 : 32;
+                for (uint32_t kb = 0; kb < cnt; ++kb) {
+                    const bool hb = (hx & (1u << kb)) != 0;
+                    const uint64_t bh = ballot(hb);
+                    const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(k0 + kb)) + lanes_below(bh);
+                    const uint32_t lim = (uint32_t)__builtin_amdgcn_readlane((int)end, (int)(k0 + kb));
+                    const uint32_t fl = x0.cb < 4 ? ((mx >> kb) & 1u ? 0u : kBmMismatch) : kBmIns;
+                    if (hb && e < lim) bm[e] = t | fl;
+                    cur += lane == k0 + kb ? (uint32_t)__builtin_popcountll(bh) : 0u;
+                }
+            }
+            base += (uint32_t)__builtin_popcountll(bb);
+            x0 = x1, x1 = x2, h = h1;
+        }
+    }
+}
+
 // emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag.
 // qual (KArgs::qual, may be null): the quality byte of every base written;
 // PS (the pass-statistics kernels, KArgs::pstat set): the reads' pass records
-// take these columns
-template <bool PS>
+// take these columns; BM (the map kernels, KArgs::bmap set; pass records where
+// KArgs::pstat is set too): the reads' bases in these columns get their map
+// entries, from the cursors as the round found them (zi: the ZMW's index)
+template <bool PS, bool BM>
 __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
-                                     uint32_t &ol)
+                                     uint32_t &ol, uint32_t zi)
 {
-    if constexpr (PS) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
+    if constexpr (BM) {
+        if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
+        base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
+    } else if constexpr (PS) {
+        pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
+    }
     uint8_t *qual = a.qual ? a.qual + z.d.out_off : nullptr;
     const uint32_t lane = lane_id(), nw = z.d.nw;
     const uint8_t *cons = P<uint8_t>(z, z.L.cons);
@@ -3246,7 +3319,10 @@ __device__ __forceinline__ void write_msa(Z &z, uint32_t ncols, uint32_t n, uint
 // kernels every other launch runs are compiled from exactly the code they were
 // before (the branch alone moved the register allocation of the whole kernel:
 // +0.2 % per launch with the feature off).
-template <bool RD_HBM, bool PS>
+// BM: the instance that writes the subread-to-CCS map (SPEC.md §11, KArgs::bmap
+// set), again a kernel of its own; in it the pass records are a branch on
+// KArgs::pstat, so that an object carries one more kernel per instance, not two.
+template <bool RD_HBM, bool PS, bool BM = false>
 __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
 {
     if (blockIdx.x >= a.nzmw) return;
@@ -3300,7 +3376,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
     uint32_t *rdoff = P<uint32_t>(z, z.L.rdoff), *rdlen = P<uint32_t>(z, z.L.rdlen);
     uint8_t *out = a.out + z.d.out_off;
     uint32_t ol = 0;
-    if constexpr (PS) {
+    if (BM ? a.pstat != nullptr : PS) {
         // the pass records accumulate over the emit calls: a slice launched again starts from zero
         uint32_t *ps = a.pstat + (size_t)z.d.seg0 * kPassWords;
         for (uint32_t x = lane; x < n * kPassWords; x += 64) ps[x] = 0;
@@ -3313,7 +3389,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit<PS>(z, ncols, ncols, n, false, out, a, ol);
+            emit<PS, BM>(z, ncols, ncols, n, false, out, a, ol, zi);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3363,7 +3439,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit<PS>(z, i, ncols, n, flag, out, a, ol);
+            emit<PS, BM>(z, i, ncols, n, flag, out, a, ol, zi);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {
@@ -3399,6 +3475,13 @@ ccsx_zmw_kernel_ps(KArgs a)
     zmw_body<false, true>(a, smem);
 }
 
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_bm(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<false, false, true>(a, smem);
+}
+
 #ifndef CCSX_RING16  // (solo16 takes LDS-instance slices only: ccsx_gpu.cpp stage_slot)
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
 ccsx_zmw_kernel_hbm(KArgs a)
@@ -3412,6 +3495,13 @@ ccsx_zmw_kernel_hbm_ps(KArgs a)
 {
     extern __shared__ int32_t smem[];
     zmw_body<true, true>(a, smem);
+}
+
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_hbm_bm(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<true, false, true>(a, smem);
 }
 #endif
 
@@ -3436,12 +3526,15 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
 {
     namespace K = ccsx::CCSX_KCFG;
     if (lds_bytes < (uint32_t)K::kLdsFixed * 4u) return hipErrorInvalidValue;
-    // KArgs::pstat selects the pass-statistics kernels
-    void (*k)(ccsx::KArgs) = a->pstat ? &K::ccsx_zmw_kernel_ps : &K::ccsx_zmw_kernel;
+    // KArgs::bmap selects the map kernels (which branch on KArgs::pstat), else
+    // KArgs::pstat the pass-statistics kernels
+    if (a->bmap && !a->bmoff) return hipErrorInvalidValue;
+    void (*k)(ccsx::KArgs) = a->bmap ? &K::ccsx_zmw_kernel_bm : a->pstat ? &K::ccsx_zmw_kernel_ps : &K::ccsx_zmw_kernel;
 #ifdef CCSX_RING16
     if (!a->lds_read_words) return hipErrorInvalidValue;
 #else
-    if (!a->lds_read_words) k = a->pstat ? &K::ccsx_zmw_kernel_hbm_ps : &K::ccsx_zmw_kernel_hbm;
+    if (!a->lds_read_words)
+        k = a->bmap ? &K::ccsx_zmw_kernel_hbm_bm : a->pstat ? &K::ccsx_zmw_kernel_hbm_ps : &K::ccsx_zmw_kernel_hbm;
 #endif
     if (lds_bytes > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,

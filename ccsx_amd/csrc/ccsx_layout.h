@@ -130,6 +130,10 @@ CCSX_HD inline uint8_t qual_phred(uint32_t match, uint32_t cov)
 // the words of ccsx_pass_stat (ccsx_gpu.h) in its order
 enum PassWord : uint32_t { kPsMatch = 0, kPsMismatch, kPsIns, kPsDel, kPsCbeg, kPsCend, kPassWords };
 
+// Subread-to-CCS coordinate map (SPEC.md §11): one word per pushed base, the
+// CCS offset in bits 0..29 (kBmOffMask) and the two flags
+constexpr uint32_t kBmOffMask = (1u << 30) - 1u, kBmMismatch = 1u << 30, kBmIns = 1u << 31;
+
 // The extension regions, in order (offsets relative to ZLayout::ext):
 //  * the far rows' slot records (rows with more than four predecessors or one
 //    beyond the DP ring, whose 8-bit cell records carry no tags): per cell the
@@ -274,6 +278,8 @@ struct KArgs {
     uint32_t *bplog;           // optional: per-round breakpoint log (main.c:619-620, ZmwDesc::bp_off)
     uint8_t *qual;             // optional: a quality byte (0..kQMax, not ASCII) per CCS byte, same offsets as out
     uint32_t *pstat;           // optional: kPassWords words per segment at (ZmwDesc::seg0 + k) * kPassWords (SPEC.md §10)
+    uint32_t *bmap;            // optional: a map word per pushed base (SPEC.md §11); the ZMW's segments back to back at bmoff[zmw]
+    const uint64_t *bmoff;     // with bmap: per ZMW, the word offset of its map (the pushed bases of the ZMWs before it)
 };
 
 // phase counters written when KArgs::prof != nullptr

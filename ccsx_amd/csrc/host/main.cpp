@@ -123,6 +123,7 @@ struct Zmw {
     std::string qual;         // -q: the CCS bases' qualities, Q + 33
     double rq = 0;            // -q: predicted accuracy of the read (ccsx_qual_rq)
     std::vector<ccsx_pass_stat> pst;  // -r: one record per segment (SPEC.md section 10)
+    std::string paf;          // -a: the PAF lines of its segments (SPEC.md section 11)
     int32_t status = 0;
     std::vector<uint32_t> bp;  // -v >= 3: (breakpoint, MSA columns) per shredding round
 };
@@ -167,6 +168,7 @@ int usage()
             "-P             primitive bsalign,subread shred by default \n"
             "-q             Output fastq: per-base consensus qualities (Q+33), np= and rq= in the header \n"
             "-r     <file>  Pass report (tab-separated): per subread, its match/mismatch/ins/del counts against the CCS, the CCS stretch it covers, identity \n"
+            "-a     <file>  Subread-to-CCS alignments (PAF, cg:Z: with =/X/I/D): per subread, where its bases lie in the CCS by the alignment the CCS was called from \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
             "\n"
@@ -462,10 +464,11 @@ int main(int argc, char **argv)
     int c, verbose = 0, min_subread_len = 5000, max_subread_len = 500000, min_fulllen_count = 3, nthreads = 1;
     int isbam = 1, split_subread = 1, fastq = 0;
     const char *report_path = nullptr;  // -r
+    const char *paf_path = nullptr;     // -a
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -473,6 +476,7 @@ int main(int argc, char **argv)
         case 'A': isbam = 0; break;
         case 'q': fastq = 1; break;
         case 'r': report_path = optarg; break;
+        case 'a': paf_path = optarg; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -517,6 +521,11 @@ int main(int argc, char **argv)
     }
     FILE *fp_rep = report_path ? fopen(report_path, "w") : nullptr;
     if (report_path && !fp_rep) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    FILE *fp_paf = paf_path ? fopen(paf_path, "w") : nullptr;
+    if (paf_path && !fp_paf) {
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
@@ -620,7 +629,7 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
-        bool qfail = false;  // -q / -r: the batch's qualities or pass records are missing (a context error)
+        bool qfail = false;  // -q / -r / -a: the batch's qualities, pass records or maps are missing (a context error)
         if (r == 0 || r == -2) {
             // -2: some ZMWs failed on the device, the rest are valid
             uint64_t cells = 0;
@@ -650,6 +659,36 @@ int main(int argc, char **argv)
                         break;
                     }
                     z.pst.assign(st, st + ns);
+                }
+                if (fp_paf && !f.out[i].status) {
+                    // one PAF line per segment with an aligned base; query
+                    // coordinates on the subread's own strand, CIGAR in CCS order
+                    std::string cg;
+                    char head[160];
+                    for (size_t k = 0; k < z.seg_len.size() && !qfail; ++k) {
+                        const uint32_t *mp = nullptr;
+                        uint32_t ml = 0;
+                        if (ccsx_gpu_base_map(ctx[w], f.slot, i, (uint32_t)k, &mp, &ml) != 0 || ml != z.seg_len[k]) {
+                            qfail = true;
+                            break;
+                        }
+                        ccsx_map_aln a;
+                        const long n = ccsx_map_cigar(mp, ml, &a, nullptr, 0);
+                        if (n < 0) continue;
+                        cg.resize((size_t)n + 1);
+                        (void)ccsx_map_cigar(mp, ml, &a, &cg[0], cg.size());
+                        cg.resize((size_t)n);
+                        const bool rev = z.seg_rev[k] != 0;
+                        snprintf(head, sizeof head, "/%zu\t%u\t%u\t%u\t%c\t", k, ml, rev ? ml - a.qe : a.qs, rev ? ml - a.qs : a.qe,
+                                 rev ? '-' : '+');
+                        z.paf += z.movie + "/" + z.hole + head + z.movie + "/" + z.hole + "/ccs";
+                        snprintf(head, sizeof head, "\t%u\t%u\t%u\t%u\t%u\t255\tsb:i:%u\tcg:Z:", f.out[i].len, a.ts, a.te, a.n_eq,
+                                 a.n_eq + a.n_x + a.n_ins + a.n_del, z.seg_off[k]);
+                        z.paf += head;
+                        z.paf += cg;
+                        z.paf += '\n';
+                    }
+                    if (qfail) break;
                 }
                 const uint32_t *lg;
                 uint32_t nr = 0;
@@ -846,6 +885,7 @@ int main(int argc, char **argv)
             if (verbose > 2 && split_subread) ccsx_gpu_set_bp_log(ctx[i], 1);
             if (fastq) ccsx_gpu_set_quality(ctx[i], 1);
             if (fp_rep) ccsx_gpu_set_pass_stats(ctx[i], 1);
+            if (fp_paf) ccsx_gpu_set_base_map(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
@@ -914,6 +954,7 @@ int main(int argc, char **argv)
                                     z.hole.c_str(), k, z.seg_off[k], z.seg_len[k], p.match, p.mismatch, p.ins, p.del, p.cbeg,
                                     p.cend, ccsx_pass_identity(&p));
                         }
+                    if (fp_paf) fwrite(z.paf.data(), 1, z.paf.size(), fp_paf);
                 }
             }
             if (timing) fprintf(stderr, "[ccsx] chunk %zu written at %.0f ms\n", ch->id, now_ms());
@@ -988,6 +1029,7 @@ int main(int argc, char **argv)
         // a failed final write (ENOSPC, EPIPE on a FIFO) must not exit 0
         bool werr = fp_out != stdout && (ferror(fp_out) || fclose(fp_out) != 0);
         if (fp_rep) werr = (ferror(fp_rep) || fclose(fp_rep) != 0) || werr;
+        if (fp_paf) werr = (ferror(fp_paf) || fclose(fp_paf) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1028,6 +1070,7 @@ int main(int argc, char **argv)
     if (fp_out != stdout) (void)fclose(fp_out);
     else (void)fflush(stdout);
     if (fp_rep) (void)fclose(fp_rep);
+    if (fp_paf) (void)fclose(fp_paf);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

@@ -30,10 +30,12 @@ EXPORTS = {
                    "ccsx_gpu_run_stats", "ccsx_gpu_zmw_bytes", "ccsx_gpu_set_slot_budget", "ccsx_gpu_set_wg_cap",
                    "ccsx_gpu_set_shred_read_cap", "ccsx_gpu_set_mem_frac", "ccsx_gpu_set_mem_wait",
                    "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
-                   "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats"],
+                   "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats",
+                   "ccsx_gpu_set_base_map", "ccsx_gpu_base_map"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
+                    "ccsx_map_cigar",
                     "ccsx_synth_batch_make", "ccsx_synth_batch_zmws", "ccsx_synth_batch_free"],
     "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_close"],
 }
@@ -121,6 +123,12 @@ def lib() -> C.CDLL:
                                               C.POINTER(C.c_uint32)]
             L.ccsx_pass_identity.argtypes = [C.c_void_p]
             L.ccsx_pass_identity.restype = C.c_double
+        if hasattr(L, "ccsx_gpu_set_base_map"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_gpu_set_base_map.argtypes = [C.c_void_p, C.c_int]
+            L.ccsx_gpu_base_map.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_uint32,
+                                            C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
+            L.ccsx_map_cigar.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+            L.ccsx_map_cigar.restype = C.c_long
         L.ccsx_revcomp.argtypes = [C.c_char_p, C.c_uint32]
         L.ccsx_prepare.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
@@ -256,6 +264,25 @@ def pass_identity(rec) -> float:
     empty one."""
     r = np.ascontiguousarray(np.asarray(rec, dtype=np.uint32).reshape(6))
     return float(lib().ccsx_pass_identity(r.ctypes.data))
+
+
+def map_cigar(m):
+    """ccsx_map_cigar: the alignment of one segment to the CCS derived from its
+    map (Engine.base_map; SPEC.md §11): a dict with qs, qe, ts, te, n_eq, n_x,
+    n_ins, n_del and cigar (=/X/I/D, in CCS order), or None for a map without
+    an aligned entry."""
+    a = np.ascontiguousarray(np.asarray(m, dtype=np.uint32).reshape(-1))
+    aln = (C.c_uint32 * 8)()
+    L = lib()
+    need = L.ccsx_map_cigar(a.ctypes.data, len(a), aln, None, 0)
+    if need < 0:
+        return None
+    buf = C.create_string_buffer(need + 1)
+    if L.ccsx_map_cigar(a.ctypes.data, len(a), aln, buf, need + 1) != need:
+        raise RuntimeError("ccsx_map_cigar: inconsistent length")
+    d = dict(zip(("qs", "qe", "ts", "te", "n_eq", "n_x", "n_ins", "n_del"), (int(x) for x in aln)))
+    d["cigar"] = buf.value.decode()
+    return d
 
 
 def read_calls(path: str, is_bam: bool = False):
@@ -554,6 +581,32 @@ class Engine:
         if not n.value:
             return np.zeros((0, 6), np.uint32)
         return np.frombuffer(C.string_at(p, n.value * 24), dtype=np.uint32).reshape(n.value, 6).copy()
+
+    def set_base_map(self, on: bool = True) -> None:
+        """The subread-to-CCS coordinate map for the following stage / run /
+        submit calls (ccsx_gpu_set_base_map): one uint32 per pushed base (SPEC.md
+        §11), read with base_map()."""
+        if self._L.ccsx_gpu_set_base_map(self._ctx, 1 if on else 0) != 0:
+            self._err("ccsx_gpu_set_base_map")
+
+    def base_map(self, i: int, slot: int = -1) -> list:
+        """The map of ZMW i: one read-only uint32 array per segment in push
+        order, seg_len[k] words in base order (bits 0..29 the CCS offset, bit 30
+        mismatch, bit 31 insertion): of the last run() / fetch() (slot -1) or of
+        the batch collected from `slot`; raises if that batch ran with the map
+        off or the ZMW failed."""
+        segs = []
+        while True:
+            p = C.POINTER(C.c_uint32)()
+            n = C.c_uint32(0)
+            if self._L.ccsx_gpu_base_map(self._ctx, slot, i, len(segs), C.byref(p), C.byref(n)) != 0:
+                # (every refusal but "segment beyond the ZMW's" also refuses segment 0)
+                if not segs:
+                    self._err("ccsx_gpu_base_map")
+                return segs
+            a = np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.zeros(0, np.uint32)
+            a.setflags(write=False)
+            segs.append(a)
 
     def set_fault(self, i: int) -> None:
         """Test hook (ccsx_gpu_set_fault): the next run() / submit() reports ZMW

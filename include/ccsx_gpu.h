@@ -158,6 +158,39 @@ typedef struct {
 } ccsx_pass_stat;
 int ccsx_gpu_set_pass_stats(ccsx_ctx *ctx, int on);
 int ccsx_gpu_pass_stats(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_pass_stat **st, uint32_t *nseg);
+/* Subread-to-CCS coordinate map (SPEC.md section 11), off by default: where
+ * every base of every pushed segment lies in the CCS, as the MSA the CCS was
+ * called from places it.  on != 0: the following ccsx_gpu_stage* /
+ * ccsx_gpu_run / ccsx_gpu_submit calls give every ZMW one 32-bit word per
+ * pushed base: bits 0..29 the offset of the CCS base the subread base is
+ * aligned to (or, with CCSX_MAP_INS, of the CCS base it is inserted before;
+ * that may be the CCS length), bit 30 (CCSX_MAP_MISMATCH) aligned to a
+ * different base, bit 31 (CCSX_MAP_INS) inserted; never both.  4 bytes per
+ * base on the device and in the pinned host output, written once per launch by
+ * the kernel's emission and copied back with the CCS.  With the map on,
+ * ccsx_gpu_zmw_bytes, the batch size ccsx_gpu_submit checks against
+ * ccsx_gpu_slot_bytes and ccsx_gpu_staged_bytes include exactly 4 x the sum of
+ * seg_len per ZMW -- about four times the subread bytes, so a slice holds
+ * fewer ZMWs -- (a caller sizing ccsx_gpu_reserve_staging adds the same to its
+ * out_bytes); with it off those values, the kernels launched and the bytes
+ * copied are what they are without this call.  Independent of
+ * ccsx_gpu_set_quality and ccsx_gpu_set_pass_stats.  A batch keeps the setting
+ * it was staged or submitted with (the full-capacity re-run inside
+ * ccsx_gpu_collect included).  The bspoa-compatible single-POA mode
+ * (ccsx_bspoa.h) has no map.
+ * ccsx_gpu_base_map: the *len = seg_len[seg] words of segment `seg` of ZMW
+ * `zmw` of a batch, in base order (of the segment as pushed): slot -1 = the
+ * last ccsx_gpu_run or ccsx_gpu_fetch on this context, 0 / 1 = that slot's
+ * last collected ccsx_gpu_submit batch.  ctx-owned, valid as long as that
+ * batch's out[i].ccs.  Returns -1 (ccsx_gpu_error says why) if the batch ran
+ * with the map off, is not collected yet, has no ZMW `zmw`, that ZMW failed
+ * (status != 0), or seg >= its nseg.  ccsx_map_cigar (ccsx_host.h) derives an
+ * alignment from a segment's map. */
+#define CCSX_MAP_OFFSET 0x3FFFFFFFu
+#define CCSX_MAP_MISMATCH 0x40000000u
+#define CCSX_MAP_INS 0x80000000u
+int ccsx_gpu_set_base_map(ccsx_ctx *ctx, int on);
+int ccsx_gpu_base_map(ccsx_ctx *ctx, int slot, size_t zmw, uint32_t seg, const uint32_t **map, uint32_t *len);
 /* The same in three steps (one slice, tight capacities, no re-run), so inputs
  * can stay resident in HBM across launches (used by bench.py).
  * ccsx_gpu_launch returns the kernel time measured with HIP events on the
@@ -172,7 +205,7 @@ int ccsx_gpu_launch(ccsx_ctx *ctx, int mode, float *kernel_ms);
 int ccsx_gpu_fetch(ccsx_ctx *ctx, ccsx_zmw_out *out);
 
 /* Device bytes the staged batch occupies (workspace + arenas; the quality
- * plane and the pass records when the batch has them). */
+ * plane, the pass records and the base map when the batch has them). */
 uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *ctx);
 
 /* Diagnostics: per-phase shader-clock counters (s_memtime) summed over the
@@ -231,7 +264,8 @@ int ccsx_gpu_run_stats(const ccsx_ctx *ctx, uint64_t *stats, uint32_t n);
 int ccsx_gpu_set_mem_wait(ccsx_ctx *ctx, uint32_t ms);
 /* Device bytes ZMW *z occupies in a ccsx_gpu_run slice of `mode` (tight
  * capacities: workspace, subreads, output slab -- twice with quality on --,
- * tables, 24 bytes per segment with pass statistics on). */
+ * tables, 24 bytes per segment with pass statistics on, 4 bytes per pushed
+ * base with the base map on). */
 uint64_t ccsx_gpu_zmw_bytes(const ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z);
 /* Test hook: bytes per slot for ccsx_gpu_run's slices (0 = by device memory:
  * half of this context's share, ccsx_gpu_set_mem_share), so a small batch is

@@ -66,6 +66,24 @@ double ccsx_qual_rq(const uint8_t *qual, uint32_t len);
  * double; 0.0 when the record is empty (or st is NULL). */
 double ccsx_pass_identity(const ccsx_pass_stat *st);
 
+/* The alignment of one segment to the CCS derived from its map (SPEC.md
+ * section 11; map / len from ccsx_gpu_base_map).  Aligned entries are those
+ * without CCSX_MAP_INS: qs = the first one's index, qe = one past the last
+ * one's, ts = entry qs's offset, te = entry qe-1's offset + 1; insertions
+ * before qs and from qe on lie outside the alignment.  The CIGAR walks
+ * [qs, qe) in CCS order: 'I' for an insertion; for an aligned entry first 'D'
+ * x (offset - previous aligned offset - 1) if positive, then 'X' with
+ * CCSX_MAP_MISMATCH, else '='; equal adjacent operations merged, lengths in
+ * decimal.  n_eq / n_x / n_ins / n_del count the operations' bases.
+ * Returns the CIGAR's length without the NUL, computed even when cap is too
+ * small; at most cap bytes are written (NUL-terminated when cap > 0, cut short
+ * if it does not fit; cigar may be NULL with cap 0).  Returns -1, *aln zeroed
+ * and an empty string, for a map without an aligned entry.  aln may be NULL. */
+typedef struct {
+    uint32_t qs, qe, ts, te, n_eq, n_x, n_ins, n_del;
+} ccsx_map_aln;
+long ccsx_map_cigar(const uint32_t *map, uint32_t len, ccsx_map_aln *aln, char *cigar, size_t cap);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
