@@ -86,7 +86,7 @@ void push_bspoa(BSPOA *g, char *seq, uint32_t len)
 void end_bspoa(BSPOA *g)
 {
     auto *im = static_cast<Impl *>(g->impl);
-    ccsx_zmw_in z{im->seqs.data(), im->off.data(), im->len.data(), (uint32_t)im->len.size()};
+    ccsx_zmw_in z{im->seqs.data(), im->off.data(), im->len.data(), (uint32_t)im->len.size(), nullptr};
     const uint8_t *cns = nullptr, *msa = nullptr;
     uint32_t ncns = 0, ncols = 0;
     if (ccsx_gpu_single_poa(im->ctx, &z, &cns, &ncns, &msa, &ncols)) die("end_bspoa", ccsx_gpu_error(im->ctx));

@@ -229,6 +229,29 @@ struct MapSet {
     }
 };
 
+// The gathered strand pileups (SPEC.md §12) of one ccsx_gpu_run call or one
+// collected batch, per ZMW of the call in input order
+struct PileSet {
+    std::vector<ccsx_pileup> recs;  // a record per CCS base, the ZMWs back to back
+    std::vector<uint64_t> off;      // per ZMW: record offset into recs
+    std::vector<uint32_t> len;      // per ZMW: records (= its CCS length)
+    std::vector<uint8_t> ok;        // per ZMW: it has a result (status 0)
+    void reset(size_t nz)
+    {
+        recs.clear();
+        off.assign(nz, 0);
+        len.assign(nz, 0);
+        ok.assign(nz, 0);
+    }
+    void put(size_t g, const ccsx_pileup *rec, uint32_t n)
+    {
+        off[g] = recs.size();
+        len[g] = n;
+        ok[g] = 1;
+        recs.insert(recs.end(), rec, rec + n);
+    }
+};
+
 // One staged slice and everything it owns on the device and the host.  A
 // context has two: ccsx_gpu_run stages and launches slice k + 1 on the other
 // slot's stream while slice k's kernel runs, so one slice's tail (the launch
@@ -266,11 +289,27 @@ struct Slot {
     uint64_t bm_bytes() const { return bmap ? nbase_total * 4 : 0; }
     const uint32_t *h_bmap(size_t zmw) const { return reinterpret_cast<const uint32_t *>(h_out.p + bm_off()) + hbmoff[zmw]; }
     std::vector<uint64_t> hbmoff;
+    // staged with the strand pileup (ccsx_gpu_set_pileup): kPuBytes per byte of
+    // the output slab in d_pile, the record of a base at its slab offset, and a
+    // strand flag per segment in d_srev (hsrev: the host copy, the index space of
+    // hlen); in h_out at pu_off(), behind the map, the flags behind the records
+    bool pile = false;
+    uint64_t pu_off() const
+    {
+        return ((bmap ? bm_off() + bm_bytes() : pstat ? pst_off() + pst_bytes() : out_bytes * (qual ? 2 : 1)) + 7) & ~uint64_t(7);
+    }
+    uint64_t pu_bytes() const { return pile ? out_bytes * ccsx::kPuBytes : 0; }
+    uint64_t srev_bytes() const { return pile ? uint64_t(nseg_total) : 0; }
+    const ccsx_pileup *h_pile(size_t zmw) const
+    {
+        return reinterpret_cast<const ccsx_pileup *>(h_out.p + pu_off()) + desc[zmw].out_off;
+    }
+    std::vector<uint8_t> hsrev;
     std::vector<ccsx::ZmwDesc> desc;
     std::vector<uint32_t> hoff, hlen, order;  // host copies the async H2D reads from
     DevBuf d_prof, d_bp;
     DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells, d_pstat;
-    DevBuf d_bmap, d_bmoff;
+    DevBuf d_bmap, d_bmoff, d_pile, d_srev;
     HostBuf h_out, h_seq;
     std::vector<uint32_t> h_olen, h_ncols, h_bp;
     std::vector<int32_t> h_status;
@@ -279,7 +318,7 @@ struct Slot {
     void release()
     {
         DevBuf *bufs[] = {&d_bp, &d_prof, &d_seq, &d_soff, &d_slen, &d_desc, &d_order, &d_ws, &d_out,
-                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_pstat, &d_bmap, &d_bmoff};
+                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_pstat, &d_bmap, &d_bmoff, &d_pile, &d_srev};
         for (DevBuf *b : bufs) b->release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -342,6 +381,10 @@ struct ccsx_ctx {
     // ccsx_gpu_base_map(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
     int last_bm = 0;
     MapSet run_bm;                     // ccsx_gpu_run's gathered maps
+    bool pileup = false;               // stage the strand pileup beside the CCS (ccsx_gpu_set_pileup)
+    // ccsx_gpu_pileup(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
+    int last_pu = 0;
+    PileSet run_pu;                    // ccsx_gpu_run's gathered pileups
     std::vector<uint32_t> run_bp;      // ccsx_gpu_run: the gathered logs, (i, ncols) pairs
     std::vector<uint64_t> run_bp_off;  // per ZMW of the call: offset into run_bp (pairs)
     std::vector<uint32_t> run_bp_n;    // per ZMW of the call: rounds
@@ -365,6 +408,9 @@ struct ccsx_ctx {
         bool bmap = false;             // submitted with the subread-to-CCS map on
         bool has_bm = false;           // collected, and bm holds its maps
         MapSet bm;
+        bool pile = false;             // submitted with the strand pileup on
+        bool has_pu = false;           // collected, and pu holds its pileups
+        PileSet pu;
     } tk[2];
 };
 
@@ -517,7 +563,7 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::zlayout(L, d);
     return ccsx::align256(L.total) + hi + d.outcap + (c->quality ? d.outcap : 0u) + uint64_t(zi.nseg) * 8 +
            (c->pass_stats ? uint64_t(zi.nseg) * ccsx::kPassWords * 4 : 0u) + (c->base_map ? S * 4 : 0u) +
-           sizeof(ccsx::ZmwDesc) + 32;
+           (c->pileup ? uint64_t(d.outcap) * ccsx::kPuBytes + zi.nseg : 0u) + sizeof(ccsx::ZmwDesc) + 32;
 }
 
 // The bytes a slice staged into slot s may need now: the device's free memory
@@ -530,7 +576,7 @@ static int slot_avail(ccsx_ctx *c, const Slot &s, uint64_t &avail)
 {
     size_t freeb = 0, totb = 0;
     HIPCHK(c, hipMemGetInfo(&freeb, &totb));
-    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap + s.d_pstat.cap + s.d_bmap.cap;
+    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap + s.d_pstat.cap + s.d_bmap.cap + s.d_pile.cap;
     avail = have > (1ull << 30) ? have - (1ull << 30) : 0;
     return 0;
 }
@@ -618,6 +664,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     s.pstat = c->pass_stats && !with_msa;
     const uint64_t pst_b = s.pst_bytes();
     const uint64_t bm_b = s.bm_bytes();
+    s.pile = c->pileup && !with_msa;
+    const uint64_t pu_b = s.pu_bytes() + s.srev_bytes();
     // 2-bit read buffer (ccsx_kernel.hip stage_read); at least one band:
     // every lane reads its window bytes even when the read is shorter.  A
     // slice with a read or a cursor array beyond the LDS budget runs the
@@ -673,7 +721,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + qual_b + pst_b + bm_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 +
+    const uint64_t need = seq_b + ws_b + out_b + qual_b + pst_b + bm_b + pu_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 +
                           nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
@@ -705,6 +753,10 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     if (s.bmap) {
         HIPCHK(c, s.d_bmap.reserve(bm_b));
         HIPCHK(c, s.d_bmoff.reserve(nz * 8));
+    }
+    if (s.pile) {
+        HIPCHK(c, s.d_pile.reserve(s.pu_bytes()));
+        HIPCHK(c, s.d_srev.reserve(s.srev_bytes()));
     }
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
@@ -793,6 +845,14 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, hipMemcpyAsync(s.d_slen.p, s.hlen.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_desc.p, s.desc.data(), nz * sizeof(ccsx::ZmwDesc), hipMemcpyHostToDevice, s.stream));
     if (s.bmap && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
+    if (s.pile) {
+        // the strand flags, read only here: a ZMW without them is all forward
+        s.hsrev.assign(nseg, 0);
+        for (size_t i = 0; i < nz; ++i)
+            if (z[i].seg_rev)
+                for (uint32_t k = 0; k < z[i].nseg; ++k) s.hsrev[s.desc[i].seg0 + k] = z[i].seg_rev[k] ? 1 : 0;
+        if (nseg) HIPCHK(c, hipMemcpyAsync(s.d_srev.p, s.hsrev.data(), nseg, hipMemcpyHostToDevice, s.stream));
+    }
     // launch order: decreasing estimated POA work (ccsx_zmw_cost: S x (28 +
     // n)), ties in input order -- longest-processing-time first, so a launch
     // ends on its cheapest ZMWs
@@ -837,6 +897,9 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     // (a slice without a pushed base has no map to write: the feature-off kernels run it)
     a.bmap = s.bm_bytes() ? s.d_bmap.as<uint32_t>() : nullptr;
     a.bmoff = s.bm_bytes() ? s.d_bmoff.as<uint64_t>() : nullptr;
+    // (likewise a slice without an output byte has no record to write)
+    a.pile = s.pu_bytes() ? s.d_pile.as<uint8_t>() : nullptr;
+    a.srev = s.pu_bytes() && s.srev_bytes() ? s.d_srev.as<uint8_t>() : nullptr;
     if (c->profiling) {
         HIPCHK(c, s.d_prof.reserve(s.nz * ccsx::kProfSlots * 8));
         a.prof = s.d_prof.as<unsigned long long>();
@@ -862,8 +925,10 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
     const size_t nz = s.nz;
     const uint64_t planes = s.qual ? 2 : 1;  // the quality plane follows the CCS plane, one copy for both
     // (the pass records follow the planes, 8-byte aligned)
-    // (and the map follows those, 8-byte aligned)
-    HIPCHK(c, s.h_out.reserve(s.bmap    ? s.bm_off() + s.bm_bytes()
+    // (and the map follows those, 8-byte aligned, and the pileup records with
+    // the strand flags behind them follow that, 8-byte aligned)
+    HIPCHK(c, s.h_out.reserve(s.pile    ? s.pu_off() + s.pu_bytes() + s.srev_bytes()
+                              : s.bmap  ? s.bm_off() + s.bm_bytes()
                               : s.pstat ? s.pst_off() + s.pst_bytes()
                                         : s.out_bytes * planes,
                               c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
@@ -880,6 +945,11 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
             HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pst_off(), s.d_pstat.p, s.pst_bytes(), hipMemcpyDeviceToHost, s.stream));
         if (s.bm_bytes())
             HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.bm_off(), s.d_bmap.p, s.bm_bytes(), hipMemcpyDeviceToHost, s.stream));
+        if (s.pu_bytes())
+            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pu_off(), s.d_pile.p, s.pu_bytes(), hipMemcpyDeviceToHost, s.stream));
+        if (s.pu_bytes() && s.srev_bytes())
+            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pu_off() + s.pu_bytes(), s.d_srev.p, s.srev_bytes(), hipMemcpyDeviceToHost,
+                                     s.stream));
         if (s.bp_words)
             HIPCHK(c, hipMemcpyAsync(s.h_bp.data(), s.d_bp.p, s.bp_words * 4, hipMemcpyDeviceToHost, s.stream));
     }
@@ -917,6 +987,7 @@ int ccsx_gpu_stage_ex(ccsx_ctx *c, const ccsx_zmw_in *z, size_t nz, int with_msa
     c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
     c->last_pst = 0;
     c->last_bm = 0;
+    c->last_pu = 0;
     const int r = stage_slot(c, s, z, nz, with_msa, full_caps);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(s.stream));
@@ -970,8 +1041,9 @@ int ccsx_gpu_fetch(ccsx_ctx *c, ccsx_zmw_out *out)
     c->last_qual = 0;
     c->last_pst = 0;
     c->last_bm = 0;
+    c->last_pu = 0;
     const int r = fetch_slot(c, c->slot[0], out);
-    if (r == 0 || r == -2) c->last_qual = c->last_pst = c->last_bm = 2;
+    if (r == 0 || r == -2) c->last_qual = c->last_pst = c->last_bm = c->last_pu = 2;
     return r;
 }
 
@@ -1067,6 +1139,8 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     c->run_pst.reset(c->pass_stats ? nz : 0);
     c->last_bm = 0;
     c->run_bm.reset(c->base_map ? nz : 0);
+    c->last_pu = 0;
+    c->run_pu.reset(c->pileup ? nz : 0);
     c->run_bp.clear();
     c->run_bp_off.assign(nz, 0);
     c->run_bp_n.assign(nz, 0);
@@ -1130,6 +1204,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             }
             if (s.pstat) c->run_pst.put(g, s.h_pstat(i), s.desc[i].n);
             if (s.bmap) c->run_bm.put(g, s.h_bmap(i), s.hlen.data() + s.desc[i].seg0, s.desc[i].n);
+            if (s.pile) c->run_pu.put(g, s.h_pile(i), o[i].len);
             if (s.bp_words && mode == CCSX_MODE_SHRED) {
                 const uint32_t *lg = s.h_bp.data() + s.desc[i].bp_off;
                 c->run_bp_off[g] = c->run_bp.size() / 2;
@@ -1281,6 +1356,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
         if (c->quality) c->run_qlen[c->fault] = 0;
         if (c->pass_stats) c->run_pst.ok[c->fault] = 0;
         if (c->base_map) c->run_bm.ok[c->fault] = 0;
+        if (c->pileup) c->run_pu.ok[c->fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     c->fault = -1;
@@ -1288,6 +1364,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     if (c->quality) c->last_qual = 1;
     if (c->pass_stats) c->last_pst = 1;
     if (c->base_map) c->last_bm = 1;
+    if (c->pileup) c->last_pu = 1;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1367,6 +1444,7 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     if (si == 0 && c->last_qual == 2) c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
     if (si == 0 && c->last_pst == 2) c->last_pst = 0;
     if (si == 0 && c->last_bm == 2) c->last_bm = 0;
+    if (si == 0 && c->last_pu == 2) c->last_pu = 0;
     r = stage_slot(c, s, z, nz, 0, 0);
     if (!r) r = launch_slot(c, s, mode);
     c->shred_caps = false;
@@ -1383,6 +1461,8 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     c->tk[si].has_pst = false;
     c->tk[si].bmap = s.bmap;
     c->tk[si].has_bm = false;
+    c->tk[si].pile = s.pile;
+    c->tk[si].has_pu = false;
     c->fault = -1;
     *slot = si;
     return 0;
@@ -1435,6 +1515,14 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         BaseMap(ccsx_ctx *x, bool on) : c(x), was(x->base_map) { c->base_map = on; }
         ~BaseMap() { c->base_map = was; }
     } base_map(c, t.bmap);
+    t.has_pu = false;
+    t.pu.reset(t.pile ? nz : 0);
+    struct Pileup {
+        ccsx_ctx *c;
+        bool was;
+        Pileup(ccsx_ctx *x, bool on) : c(x), was(x->pileup) { c->pileup = on; }
+        ~Pileup() { c->pileup = was; }
+    } pileup(c, t.pile);
     auto gather = [&](const ccsx_zmw_out *res, const uint32_t *idx, size_t n, bool can_retry) {
         size_t add = 0;
         for (size_t i = 0; i < n; ++i) add += res[i].status ? 0 : res[i].len;
@@ -1469,6 +1557,7 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
             // (gather's results are the slot's, in its order: ZMW i of the slot)
             if (s.pstat) t.pst.put(g, s.h_pstat(i), s.desc[i].n);
             if (s.bmap) t.bm.put(g, s.h_bmap(i), s.hlen.data() + s.desc[i].seg0, s.desc[i].n);
+            if (s.pile) t.pu.put(g, s.h_pile(i), res[i].len);
         }
     };
     gather(o.data(), nullptr, nz, true);
@@ -1514,12 +1603,14 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         if (t.qual) t.qlen[t.fault] = 0;
         if (t.pstat) t.pst.ok[t.fault] = 0;
         if (t.bmap) t.bm.ok[t.fault] = 0;
+        if (t.pile) t.pu.ok[t.fault] = 0;
         if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
     }
     for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(t.arena.data() + aoff[i]);
     t.has_qual = t.qual;
     t.has_pst = t.pstat;
     t.has_bm = t.bmap;
+    t.has_pu = t.pile;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1836,6 +1927,67 @@ int ccsx_gpu_base_map(ccsx_ctx *c, int slot, size_t zmw, uint32_t seg, const uin
     return 0;
 }
 
+int ccsx_gpu_set_pileup(ccsx_ctx *c, int on)
+{
+    if (!c) return -1;
+    c->pileup = on != 0;
+    return 0;
+}
+
+int ccsx_gpu_pileup(ccsx_ctx *c, int slot, size_t zmw, const ccsx_pileup **p, uint32_t *len)
+{
+    if (!c || !p || !len) return -1;
+    *p = nullptr;
+    *len = 0;
+    if (slot < -1 || slot > 1) {
+        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
+        return -1;
+    }
+    const char *off = "that batch ran with the pileup off (ccsx_gpu_set_pileup)";
+    const char *range = "ZMW index beyond the batch";
+    const char *failed = "that ZMW failed: it has no pileup";
+    const PileSet *ps = nullptr;
+    if (slot >= 0) {
+        const auto &t = c->tk[slot];
+        if (t.pending || !t.has_pu) {
+            c->err = t.pending ? "that slot's batch is not collected yet" : off;
+            return -1;
+        }
+        ps = &t.pu;
+    } else if (c->last_pu == 1) {
+        ps = &c->run_pu;
+    }
+    if (ps) {
+        if (zmw >= ps->len.size()) {
+            c->err = range;
+            return -1;
+        }
+        if (!ps->ok[zmw]) {
+            c->err = failed;
+            return -1;
+        }
+        *p = ps->recs.data() + ps->off[zmw];
+        *len = ps->len[zmw];
+        return 0;
+    }
+    const Slot &s = c->slot[0];
+    if (c->last_pu != 2 || !s.pile) {
+        c->err = off;
+        return -1;
+    }
+    if (zmw >= s.nz) {
+        c->err = range;
+        return -1;
+    }
+    if (s.h_status[zmw]) {
+        c->err = failed;
+        return -1;
+    }
+    *p = s.h_pile(zmw);
+    *len = s.h_olen[zmw];
+    return 0;
+}
+
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -1886,7 +2038,8 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.pst_bytes() + s.bm_bytes() + s.msa_bytes;
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.pst_bytes() + s.bm_bytes() + s.pu_bytes() + s.srev_bytes() +
+           s.msa_bytes;
 }
 
 // single-POA path used by the bspoa-compatible API (bspoa_gpu.cpp)

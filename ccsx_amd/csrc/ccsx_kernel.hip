@@ -3234,17 +3234,64 @@ __device__ __forceinline__ void base_map(const Z &z, uint32_t i, uint32_t n, uin
     }
 }
 
+// SPEC.md §12, the counts of column c (lane = column; v: c is an emitted
+// column, a lane without one counts nothing) split by the strand flags srev (a
+// byte per read of the ZMW, null: all forward): cnt[s][b] the reads of strand s
+// with base b in the column, cov[s] those spanning it.  Per 64 reads one ballot
+// over the flags gives the wave-uniform strand word; the lane walks its
+// column's rows as columns_count does and splits each row's popcount by that
+// word, then the reads' spans.  Called by every lane of the wave.
+__device__ __forceinline__ void pileup_col(const Z &z, uint32_t c, bool v, uint32_t n, const uint8_t *srev,
+                                           uint32_t (&cnt)[2][4], uint32_t (&cov)[2])
+{
+    const uint32_t lane = lane_id(), nw = z.d.nw;
+    const uint8_t *nb = G_nb(z, z.cur);
+    const uint64_t *mem = G_mem(z, z.cur);
+    const uint32_t *colrow = P<uint32_t>(z, z.L.colrow);
+    const uint32_t *rfc = P<uint32_t>(z, z.L.rfc), *rlc = P<uint32_t>(z, z.L.rlc);
+    const uint32_t ra = v ? colrow[c] : 0u, re = v ? colrow[c + 1] : 0u;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; ++b) cnt[0][b] = cnt[1][b] = 0;
+    cov[0] = cov[1] = 0;
+    for (uint32_t w = 0; w * 64 < n; ++w) {
+        const uint32_t k = w * 64 + lane;
+        const uint64_t rw = ballot(srev != nullptr && k < n && srev[k] != 0);
+        for (uint32_t u = ra; u < re; ++u) {
+            const uint64_t x = mem[(size_t)u * nw + w];
+            const uint32_t b = nb[u] & 3u;
+            const uint32_t pr = (uint32_t)__builtin_popcountll(x & rw), pf = (uint32_t)__builtin_popcountll(x & ~rw);
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) cnt[0][q] += b == q ? pf : 0u, cnt[1][q] += b == q ? pr : 0u;
+        }
+        const uint32_t kn = n - w * 64 < 64 ? n - w * 64 : 64;
+        for (uint32_t kb = 0; kb < kn; ++kb) {
+            const uint32_t kk = w * 64 + kb;
+            const uint32_t sp = (v && rfc[kk] <= c && c <= rlc[kk]) ? 1u : 0u;
+            const uint32_t r = (uint32_t)(rw >> kb) & 1u;
+            cov[0] += sp & (r ^ 1u);
+            cov[1] += sp & r;
+        }
+    }
+}
+
 // emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag.
 // qual (KArgs::qual, may be null): the quality byte of every base written;
 // PS (the pass-statistics kernels, KArgs::pstat set): the reads' pass records
 // take these columns; BM (the map kernels, KArgs::bmap set; pass records where
 // KArgs::pstat is set too): the reads' bases in these columns get their map
-// entries, from the cursors as the round found them (zi: the ZMW's index)
-template <bool PS, bool BM>
+// entries, from the cursors as the round found them (zi: the ZMW's index);
+// PU (the pileup kernels, KArgs::pile set; pass records and map where their
+// pointers are set): every base written gets its strand pileup record
+// (SPEC.md §12); pc = per strand the bases of the gap-consensus columns emitted
+// since the ZMW's last CCS base (it lives across the rounds, in the caller)
+template <bool PS, bool BM, bool PU>
 __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
-                                     uint32_t &ol, uint32_t zi)
+                                     uint32_t &ol, uint32_t zi, uint32_t (&pc)[2])
 {
-    if constexpr (BM) {
+    if constexpr (PU) {
+        if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
+        if (a.bmap) base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
+    } else if constexpr (BM) {
         if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
         base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
     } else if constexpr (PS) {
@@ -3277,6 +3324,39 @@ __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t 
             const uint32_t o = ol + lanes_below(bal);
             if (o < z.d.outcap) out[o] = (uint8_t)"ACGT"[cb];
             if (qual && o < z.d.outcap) qual[o] = column_qual(z, c, n);
+        }
+        if constexpr (PU) {
+            uint32_t cnt[2][4], cov[2];
+            pileup_col(z, c, c < i, n, a.srev ? a.srev + z.d.seg0 : nullptr, cnt, cov);
+            // ins: a gap-consensus column gives its bases, a base column takes
+            // those since the base column before it -- the difference of the
+            // inclusive sums at the two lanes, the carry pc before the chunk's
+            // first base column
+            const uint64_t lo = bal & ((1ull << lane) - 1ull);  // the base columns below this lane's
+            const uint32_t prev = lo ? 63u - (uint32_t)__builtin_clzll(lo) : 0u;
+            const uint32_t top = bal ? 63u - (uint32_t)__builtin_clzll(bal) : 0u;  // the chunk's last base column
+            uint32_t rec[2][kPuFields];
+#pragma unroll
+            for (uint32_t s = 0; s < 2; ++s) {
+                const uint32_t tot = cnt[s][0] + cnt[s][1] + cnt[s][2] + cnt[s][3];
+                const uint32_t sum = wave_incl_add(c < i && cb >= 4 ? tot : 0u);
+                const uint32_t at = (uint32_t)__shfl((int)sum, (int)prev);
+                const uint32_t ins = lo ? sum - at : sum + pc[s];
+                const uint32_t end = (uint32_t)__builtin_amdgcn_readlane((int)sum, 63);
+                const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)sum, (int)uni(top));
+                pc[s] = bal ? end - last : pc[s] + end;
+#pragma unroll
+                for (uint32_t b = 0; b < 4; ++b) rec[s][b] = sat8(cnt[s][b]);
+                rec[s][kPuGap] = sat8(cov[s] - tot);
+                rec[s][kPuIns] = sat8(ins);
+            }
+            const uint32_t o = ol + lanes_below(bal);
+            if (cb < 4 && o < z.d.outcap) {
+                uint32_t *p = reinterpret_cast<uint32_t *>(a.pile + ((size_t)z.d.out_off + o) * kPuBytes);
+                p[0] = rec[0][0] | rec[0][1] << 8 | rec[0][2] << 16 | rec[0][3] << 24;
+                p[1] = rec[0][4] | rec[0][5] << 8 | rec[1][0] << 16 | rec[1][1] << 24;
+                p[2] = rec[1][2] | rec[1][3] << 8 | rec[1][4] << 16 | rec[1][5] << 24;
+            }
         }
         ol += (uint32_t)__builtin_popcountll(bal);
     }
@@ -3322,7 +3402,10 @@ __device__ __forceinline__ void write_msa(Z &z, uint32_t ncols, uint32_t n, uint
 // BM: the instance that writes the subread-to-CCS map (SPEC.md §11, KArgs::bmap
 // set), again a kernel of its own; in it the pass records are a branch on
 // KArgs::pstat, so that an object carries one more kernel per instance, not two.
-template <bool RD_HBM, bool PS, bool BM = false>
+// PU: the instance that writes the strand pileup (SPEC.md §12, KArgs::pile
+// set), a kernel of its own for the same reason; in it the pass records and the
+// map are branches on their pointers.
+template <bool RD_HBM, bool PS, bool BM = false, bool PU = false>
 __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
 {
     if (blockIdx.x >= a.nzmw) return;
@@ -3376,7 +3459,8 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
     uint32_t *rdoff = P<uint32_t>(z, z.L.rdoff), *rdlen = P<uint32_t>(z, z.L.rdlen);
     uint8_t *out = a.out + z.d.out_off;
     uint32_t ol = 0;
-    if (BM ? a.pstat != nullptr : PS) {
+    uint32_t pc[2] = {0, 0};  // PU: emit's carry of dropped bases, per strand (zero before the ZMW's first POA call)
+    if (BM || PU ? a.pstat != nullptr : PS) {
         // the pass records accumulate over the emit calls: a slice launched again starts from zero
         uint32_t *ps = a.pstat + (size_t)z.d.seg0 * kPassWords;
         for (uint32_t x = lane; x < n * kPassWords; x += 64) ps[x] = 0;
@@ -3389,7 +3473,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit<PS, BM>(z, ncols, ncols, n, false, out, a, ol, zi);
+            emit<PS, BM, PU>(z, ncols, ncols, n, false, out, a, ol, zi, pc);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3439,7 +3523,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit<PS, BM>(z, i, ncols, n, flag, out, a, ol, zi);
+            emit<PS, BM, PU>(z, i, ncols, n, flag, out, a, ol, zi, pc);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {
@@ -3482,6 +3566,13 @@ ccsx_zmw_kernel_bm(KArgs a)
     zmw_body<false, false, true>(a, smem);
 }
 
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_pu(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<false, false, false, true>(a, smem);
+}
+
 #ifndef CCSX_RING16  // (solo16 takes LDS-instance slices only: ccsx_gpu.cpp stage_slot)
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
 ccsx_zmw_kernel_hbm(KArgs a)
@@ -3502,6 +3593,13 @@ ccsx_zmw_kernel_hbm_bm(KArgs a)
 {
     extern __shared__ int32_t smem[];
     zmw_body<true, false, true>(a, smem);
+}
+
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_hbm_pu(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<true, false, false, true>(a, smem);
 }
 #endif
 
@@ -3526,15 +3624,22 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
 {
     namespace K = ccsx::CCSX_KCFG;
     if (lds_bytes < (uint32_t)K::kLdsFixed * 4u) return hipErrorInvalidValue;
-    // KArgs::bmap selects the map kernels (which branch on KArgs::pstat), else
-    // KArgs::pstat the pass-statistics kernels
+    // KArgs::pile selects the pileup kernels (which branch on KArgs::bmap and
+    // KArgs::pstat), else KArgs::bmap the map kernels (which branch on
+    // KArgs::pstat), else KArgs::pstat the pass-statistics kernels
     if (a->bmap && !a->bmoff) return hipErrorInvalidValue;
-    void (*k)(ccsx::KArgs) = a->bmap ? &K::ccsx_zmw_kernel_bm : a->pstat ? &K::ccsx_zmw_kernel_ps : &K::ccsx_zmw_kernel;
+    void (*k)(ccsx::KArgs) = a->pile   ? &K::ccsx_zmw_kernel_pu
+                             : a->bmap ? &K::ccsx_zmw_kernel_bm
+                             : a->pstat ? &K::ccsx_zmw_kernel_ps
+                                        : &K::ccsx_zmw_kernel;
 #ifdef CCSX_RING16
     if (!a->lds_read_words) return hipErrorInvalidValue;
 #else
     if (!a->lds_read_words)
-        k = a->bmap ? &K::ccsx_zmw_kernel_hbm_bm : a->pstat ? &K::ccsx_zmw_kernel_hbm_ps : &K::ccsx_zmw_kernel_hbm;
+        k = a->pile    ? &K::ccsx_zmw_kernel_hbm_pu
+            : a->bmap  ? &K::ccsx_zmw_kernel_hbm_bm
+            : a->pstat ? &K::ccsx_zmw_kernel_hbm_ps
+                       : &K::ccsx_zmw_kernel_hbm;
 #endif
     if (lds_bytes > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -134,6 +134,14 @@ enum PassWord : uint32_t { kPsMatch = 0, kPsMismatch, kPsIns, kPsDel, kPsCbeg, k
 // CCS offset in bits 0..29 (kBmOffMask) and the two flags
 constexpr uint32_t kBmOffMask = (1u << 30) - 1u, kBmMismatch = 1u << 30, kBmIns = 1u << 31;
 
+// Per-base strand pileup (SPEC.md §12): twelve bytes per CCS base, the layout
+// of ccsx_pileup (ccsx_gpu.h): per strand (forward reads first) the reads with
+// A, C, G, T in the base's column, the spanning reads without a base there, and
+// the bases of the dropped (gap-consensus) columns before it.  Every field
+// saturates at 255: the device and the host clamp with the same function.
+constexpr uint32_t kPuBytes = 12, kPuGap = 4, kPuIns = 5, kPuFields = 6;
+CCSX_HD inline uint8_t sat8(uint32_t v) { return uint8_t(v > 255u ? 255u : v); }
+
 // The extension regions, in order (offsets relative to ZLayout::ext):
 //  * the far rows' slot records (rows with more than four predecessors or one
 //    beyond the DP ring, whose 8-bit cell records carry no tags): per cell the
@@ -280,6 +288,8 @@ struct KArgs {
     uint32_t *pstat;           // optional: kPassWords words per segment at (ZmwDesc::seg0 + k) * kPassWords (SPEC.md §10)
     uint32_t *bmap;            // optional: a map word per pushed base (SPEC.md §11); the ZMW's segments back to back at bmoff[zmw]
     const uint64_t *bmoff;     // with bmap: per ZMW, the word offset of its map (the pushed bases of the ZMWs before it)
+    uint8_t *pile;             // optional: kPuBytes per CCS byte at (ZmwDesc::out_off + offset) * kPuBytes (SPEC.md §12)
+    const uint8_t *srev;       // optional, read with pile: a strand flag per segment at ZmwDesc::seg0 + k (null: all forward)
 };
 
 // phase counters written when KArgs::prof != nullptr

@@ -68,6 +68,7 @@ uint32_t ccsx_partition(const uint64_t *cost, uint32_t n, uint32_t nparts, uint3
 struct ccsx_synth_batch {
     std::vector<std::string> seqs;
     std::vector<std::vector<uint32_t>> off, len;
+    std::vector<std::vector<uint8_t>> rev;  // the strand flags ccsx_prepare gave (ccsx_zmw_in::seg_rev)
     std::vector<ccsx_zmw_in> in;
 };
 
@@ -80,6 +81,7 @@ ccsx_synth_batch *ccsx_synth_batch_make(uint64_t seed, const uint64_t *holes, co
     b->seqs.resize(n);
     b->off.resize(n);
     b->len.resize(n);
+    b->rev.resize(n);
     b->in.resize(n);
     std::atomic<uint32_t> nx(0);
     auto work = [&]() {
@@ -92,10 +94,15 @@ ccsx_synth_batch *ccsx_synth_batch_make(uint64_t seed, const uint64_t *holes, co
             s.resize(tot);
             b->off[i].resize(passes[i]);
             b->len[i].resize(passes[i]);
-            const uint32_t ns = ccsx_prepare_apply(&s[0], lens.data(), passes[i], b->off[i].data(), b->len[i].data());
+            b->rev[i].resize(passes[i] ? passes[i] : 1);
+            // (ccsx_prepare_apply, keeping the flags)
+            const uint32_t ns = ccsx_prepare(&s[0], lens.data(), passes[i], b->off[i].data(), b->len[i].data(), b->rev[i].data());
+            for (uint32_t l = 0; l < ns; ++l)
+                if (b->rev[i][l]) ccsx_revcomp(&s[b->off[i][l]], b->len[i][l]);
             b->off[i].resize(ns);
             b->len[i].resize(ns);
-            b->in[i] = ccsx_zmw_in{s.data(), b->off[i].data(), b->len[i].data(), ns};
+            b->rev[i].resize(ns);
+            b->in[i] = ccsx_zmw_in{s.data(), b->off[i].data(), b->len[i].data(), ns, b->rev[i].data()};
         }
     };
     std::vector<std::thread> th;

@@ -124,6 +124,7 @@ struct Zmw {
     double rq = 0;            // -q: predicted accuracy of the read (ccsx_qual_rq)
     std::vector<ccsx_pass_stat> pst;  // -r: one record per segment (SPEC.md section 10)
     std::string paf;          // -a: the PAF lines of its segments (SPEC.md section 11)
+    std::string sites;        // -s: the lines of its discordant sites (SPEC.md section 12)
     int32_t status = 0;
     std::vector<uint32_t> bp;  // -v >= 3: (breakpoint, MSA columns) per shredding round
 };
@@ -169,6 +170,7 @@ int usage()
             "-q             Output fastq: per-base consensus qualities (Q+33), np= and rq= in the header \n"
             "-r     <file>  Pass report (tab-separated): per subread, its match/mismatch/ins/del counts against the CCS, the CCS stretch it covers, identity \n"
             "-a     <file>  Subread-to-CCS alignments (PAF, cg:Z: with =/X/I/D): per subread, where its bases lie in the CCS by the alignment the CCS was called from \n"
+            "-s     <file>  Strand-discordant sites (tab-separated): per CCS position whose forward and reverse subreads call different bases (or base against gap), the two calls and the per-strand A/C/G/T/gap/ins counts \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
             "\n"
@@ -465,10 +467,11 @@ int main(int argc, char **argv)
     int isbam = 1, split_subread = 1, fastq = 0;
     const char *report_path = nullptr;  // -r
     const char *paf_path = nullptr;     // -a
+    const char *site_path = nullptr;    // -s
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -477,6 +480,7 @@ int main(int argc, char **argv)
         case 'q': fastq = 1; break;
         case 'r': report_path = optarg; break;
         case 'a': paf_path = optarg; break;
+        case 's': site_path = optarg; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -526,6 +530,11 @@ int main(int argc, char **argv)
     }
     FILE *fp_paf = paf_path ? fopen(paf_path, "w") : nullptr;
     if (paf_path && !fp_paf) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    FILE *fp_site = site_path ? fopen(site_path, "w") : nullptr;
+    if (site_path && !fp_site) {
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
@@ -620,7 +629,7 @@ int main(int argc, char **argv)
         f.out.assign(f.b.idx.size(), ccsx_zmw_out{});
         for (size_t i = 0; i < f.b.idx.size(); ++i) {
             const Zmw &z = ch.zs[f.b.idx[i]];
-            f.in[i] = ccsx_zmw_in{z.seqs, z.seg_off.data(), z.seg_len.data(), (uint32_t)z.seg_len.size()};
+            f.in[i] = ccsx_zmw_in{z.seqs, z.seg_off.data(), z.seg_len.data(), (uint32_t)z.seg_len.size(), z.seg_rev.data()};
             if (!fault_hole.empty() && z.hole == fault_hole) ccsx_gpu_set_fault(ctx[w], (int64_t)i);
         }
         f.t0 = now_ms();
@@ -629,7 +638,7 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
-        bool qfail = false;  // -q / -r / -a: the batch's qualities, pass records or maps are missing (a context error)
+        bool qfail = false;  // -q / -r / -a / -s: the batch's qualities, pass records, maps or pileups are missing (a context error)
         if (r == 0 || r == -2) {
             // -2: some ZMWs failed on the device, the rest are valid
             uint64_t cells = 0;
@@ -689,6 +698,25 @@ int main(int argc, char **argv)
                         z.paf += '\n';
                     }
                     if (qfail) break;
+                }
+                if (fp_site && !f.out[i].status) {
+                    // one line per position whose two strands call differently
+                    const ccsx_pileup *pu = nullptr;
+                    uint32_t pl = 0;
+                    if (ccsx_gpu_pileup(ctx[w], f.slot, i, &pu, &pl) != 0 || pl != f.out[i].len) {
+                        qfail = true;
+                        break;
+                    }
+                    char line[160];
+                    for (uint32_t p = 0; p < pl; ++p) {
+                        const int cf = ccsx_pileup_call(&pu[p], 0), cr = ccsx_pileup_call(&pu[p], 1);
+                        if (cf < 0 || cr < 0 || cf == cr) continue;
+                        const uint8_t *a = pu[p].fwd, *b = pu[p].rev;
+                        snprintf(line, sizeof line, "/ccs\t%u\t%c\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", p,
+                                 f.out[i].ccs[p], "ACGT-"[cf], "ACGT-"[cr], a[0], a[1], a[2], a[3], a[4], a[5], b[0], b[1], b[2],
+                                 b[3], b[4], b[5]);
+                        z.sites += z.movie + "/" + z.hole + line;
+                    }
                 }
                 const uint32_t *lg;
                 uint32_t nr = 0;
@@ -886,6 +914,7 @@ int main(int argc, char **argv)
             if (fastq) ccsx_gpu_set_quality(ctx[i], 1);
             if (fp_rep) ccsx_gpu_set_pass_stats(ctx[i], 1);
             if (fp_paf) ccsx_gpu_set_base_map(ctx[i], 1);
+            if (fp_site) ccsx_gpu_set_pileup(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
@@ -955,6 +984,7 @@ int main(int argc, char **argv)
                                     p.cend, ccsx_pass_identity(&p));
                         }
                     if (fp_paf) fwrite(z.paf.data(), 1, z.paf.size(), fp_paf);
+                    if (fp_site) fwrite(z.sites.data(), 1, z.sites.size(), fp_site);
                 }
             }
             if (timing) fprintf(stderr, "[ccsx] chunk %zu written at %.0f ms\n", ch->id, now_ms());
@@ -1030,6 +1060,7 @@ int main(int argc, char **argv)
         bool werr = fp_out != stdout && (ferror(fp_out) || fclose(fp_out) != 0);
         if (fp_rep) werr = (ferror(fp_rep) || fclose(fp_rep) != 0) || werr;
         if (fp_paf) werr = (ferror(fp_paf) || fclose(fp_paf) != 0) || werr;
+        if (fp_site) werr = (ferror(fp_site) || fclose(fp_site) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1071,6 +1102,7 @@ int main(int argc, char **argv)
     else (void)fflush(stdout);
     if (fp_rep) (void)fclose(fp_rep);
     if (fp_paf) (void)fclose(fp_paf);
+    if (fp_site) (void)fclose(fp_site);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

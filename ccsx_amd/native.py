@@ -31,11 +31,11 @@ EXPORTS = {
                    "ccsx_gpu_set_shred_read_cap", "ccsx_gpu_set_mem_frac", "ccsx_gpu_set_mem_wait",
                    "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
                    "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats",
-                   "ccsx_gpu_set_base_map", "ccsx_gpu_base_map"],
+                   "ccsx_gpu_set_base_map", "ccsx_gpu_base_map", "ccsx_gpu_set_pileup", "ccsx_gpu_pileup"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
-                    "ccsx_map_cigar",
+                    "ccsx_map_cigar", "ccsx_pileup_call",
                     "ccsx_synth_batch_make", "ccsx_synth_batch_zmws", "ccsx_synth_batch_free"],
     "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_close"],
 }
@@ -43,7 +43,7 @@ EXPORTS = {
 
 class ZmwIn(C.Structure):
     _fields_ = [("seqs", C.c_char_p), ("seg_off", C.POINTER(C.c_uint32)), ("seg_len", C.POINTER(C.c_uint32)),
-                ("nseg", C.c_uint32)]
+                ("nseg", C.c_uint32), ("seg_rev", C.POINTER(C.c_uint8))]
 
 
 class ZmwOut(C.Structure):
@@ -129,6 +129,9 @@ def lib() -> C.CDLL:
                                             C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
             L.ccsx_map_cigar.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
             L.ccsx_map_cigar.restype = C.c_long
+        L.ccsx_gpu_set_pileup.argtypes = [C.c_void_p, C.c_int]
+        L.ccsx_gpu_pileup.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        L.ccsx_pileup_call.argtypes = [C.c_void_p, C.c_int]
         L.ccsx_revcomp.argtypes = [C.c_char_p, C.c_uint32]
         L.ccsx_prepare.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
@@ -193,10 +196,13 @@ def synth_zmw(seed: int, hole: int, L: int, passes: int):
 
 @dataclass
 class Prepared:
-    """One ZMW after ccs_prepare + strand flip: segments are slices of seqs."""
+    """One ZMW after ccs_prepare + strand flip: segments are slices of seqs;
+    rev = ccs_prepare's strand flag per segment (None: all forward), read by the
+    engine only with the strand pileup on."""
     seqs: bytes
     offs: np.ndarray
     lens: np.ndarray
+    rev: np.ndarray | None = None
 
 
 def prepare(subreads: list[bytes]) -> Prepared:
@@ -207,8 +213,16 @@ def prepare(subreads: list[bytes]) -> Prepared:
     n = len(subreads)
     so = np.zeros(max(n, 1), dtype=np.uint32)
     sl = np.zeros(max(n, 1), dtype=np.uint32)
-    ns = lib().ccsx_prepare_apply(buf, _p32(lens), n, _p32(so), _p32(sl))
-    return Prepared(buf.raw[:len(seqs)], so[:ns].copy(), sl[:ns].copy())
+    rv = np.zeros(max(n, 1), dtype=np.uint8)
+    # (ccsx_prepare_apply, keeping the flags)
+    L = lib()
+    ns = L.ccsx_prepare(buf, _p32(lens), n, _p32(so), _p32(sl), rv.ctypes.data_as(C.POINTER(C.c_uint8)))
+    out = bytearray(buf.raw[:len(seqs)])
+    for k in range(ns):
+        if rv[k]:
+            o, ln = int(so[k]), int(sl[k])
+            out[o:o + ln] = revcomp(bytes(out[o:o + ln]))
+    return Prepared(bytes(out), so[:ns].copy(), sl[:ns].copy(), rv[:ns].copy())
 
 
 def prepare_segments(subreads: list[bytes]):
@@ -283,6 +297,14 @@ def map_cigar(m):
     d = dict(zip(("qs", "qe", "ts", "te", "n_eq", "n_x", "n_ins", "n_del"), (int(x) for x in aln)))
     d["cigar"] = buf.value.decode()
     return d
+
+
+def pileup_call(rec, strand: int) -> int:
+    """ccsx_pileup_call: the call of strand 0 (forward) / 1 (reverse) / 2 (both)
+    from one 12-byte pileup record (Engine.pileup; SPEC.md §12): 0..3 a base, 4
+    gap, -1 no evidence."""
+    r = np.ascontiguousarray(np.asarray(rec, dtype=np.uint8).reshape(12))
+    return int(lib().ccsx_pileup_call(r.ctypes.data, strand))
 
 
 def read_calls(path: str, is_bam: bool = False):
@@ -393,6 +415,13 @@ class Engine:
             arr[i].seg_off = _p32(offs)
             arr[i].seg_len = _p32(lens)
             arr[i].nseg = len(lens)
+            rev = getattr(z, "rev", None)
+            if rev is not None:
+                rev = np.ascontiguousarray(np.asarray(rev, dtype=np.uint8))
+                if len(rev) != len(lens):
+                    raise ValueError("Prepared.rev needs one flag per segment")
+                keep.append(rev)
+                arr[i].seg_rev = rev.ctypes.data_as(C.POINTER(C.c_uint8))
         return arr, keep
 
     def stage(self, zmws: list[Prepared], mode: int | None = None) -> None:
@@ -607,6 +636,27 @@ class Engine:
             a = np.ctypeslib.as_array(p, (n.value,)).copy() if n.value else np.zeros(0, np.uint32)
             a.setflags(write=False)
             segs.append(a)
+
+    def set_pileup(self, on: bool = True) -> None:
+        """The per-base strand pileup for the following stage / run / submit
+        calls (ccsx_gpu_set_pileup): twelve bytes per CCS base (SPEC.md §12),
+        read with pileup()."""
+        if self._L.ccsx_gpu_set_pileup(self._ctx, 1 if on else 0) != 0:
+            self._err("ccsx_gpu_set_pileup")
+
+    def pileup(self, i: int, slot: int = -1) -> np.ndarray:
+        """The pileup of ZMW i, uint8 [len, 12]: per CCS base the forward reads'
+        A, C, G, T, gap, ins counts, then the reverse reads', each saturating at
+        255: of the last run() / fetch() (slot -1) or of the batch collected
+        from `slot`; raises if that batch ran with the pileup off or the ZMW
+        failed."""
+        p = C.c_void_p()
+        n = C.c_uint32(0)
+        if self._L.ccsx_gpu_pileup(self._ctx, slot, i, C.byref(p), C.byref(n)) != 0:
+            self._err("ccsx_gpu_pileup")
+        if not n.value:
+            return np.zeros((0, 12), np.uint8)
+        return np.frombuffer(C.string_at(p, n.value * 12), dtype=np.uint8).reshape(n.value, 12).copy()
 
     def set_fault(self, i: int) -> None:
         """Test hook (ccsx_gpu_set_fault): the next run() / submit() reports ZMW

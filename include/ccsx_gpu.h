@@ -43,6 +43,8 @@ typedef struct {
     const uint32_t *seg_off;  /* nseg offsets into seqs, in push order */
     const uint32_t *seg_len;  /* nseg lengths */
     uint32_t nseg;
+    const uint8_t *seg_rev;   /* nseg strand flags (1: ccs_prepare marked the segment reverse), or NULL = all
+                               * forward; read only with ccsx_gpu_set_pileup on */
 } ccsx_zmw_in;
 
 typedef struct {
@@ -191,6 +193,37 @@ int ccsx_gpu_pass_stats(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_pass_sta
 #define CCSX_MAP_INS 0x80000000u
 int ccsx_gpu_set_base_map(ccsx_ctx *ctx, int on);
 int ccsx_gpu_base_map(ccsx_ctx *ctx, int slot, size_t zmw, uint32_t seg, const uint32_t **map, uint32_t *len);
+/* Per-base strand pileup (SPEC.md section 12), off by default: the evidence
+ * behind every CCS base, as the MSA the CCS was called from holds it, split by
+ * the strand of the pushed segments (ccsx_zmw_in::seg_rev; NULL = all forward).
+ * on != 0: the following ccsx_gpu_stage* / ccsx_gpu_run / ccsx_gpu_submit calls
+ * give every ZMW one 12-byte record per byte of its output slab, device and
+ * pinned host -- per strand the reads with A, C, G, T in the base's column, the
+ * spanning reads with no base there, and the bases of the dropped columns
+ * since the CCS base before; every field saturates at 255 -- written once per
+ * launch by the kernel's emission and copied back with the CCS, and a strand
+ * flag byte per segment beside them.  With the pileup on, ccsx_gpu_zmw_bytes,
+ * the batch size ccsx_gpu_submit checks against ccsx_gpu_slot_bytes and
+ * ccsx_gpu_staged_bytes include exactly 12 x the ZMW's output slab + nseg per
+ * ZMW (a caller sizing ccsx_gpu_reserve_staging adds the same to its
+ * out_bytes); with it off those values, the kernels launched and the bytes
+ * copied are what they are without this call.  Independent of
+ * ccsx_gpu_set_quality, ccsx_gpu_set_pass_stats and ccsx_gpu_set_base_map.  A
+ * batch keeps the setting it was staged or submitted with (the full-capacity
+ * re-run inside ccsx_gpu_collect included).  The bspoa-compatible single-POA
+ * mode (ccsx_bspoa.h) has no pileup.
+ * ccsx_gpu_pileup: the *len (= that ZMW's out[i].len) records of ZMW `zmw` of
+ * a batch, record p for CCS base p: slot -1 = the last ccsx_gpu_run or
+ * ccsx_gpu_fetch on this context, 0 / 1 = that slot's last collected
+ * ccsx_gpu_submit batch.  ctx-owned, valid as long as that batch's out[i].ccs.
+ * Returns -1 (ccsx_gpu_error says why) if the batch ran with the pileup off, is
+ * not collected yet, has no ZMW `zmw`, or that ZMW failed (status != 0).
+ * ccsx_pileup_call (ccsx_host.h) derives a strand's call from a record. */
+typedef struct {
+    uint8_t fwd[6], rev[6];   /* per strand: A, C, G, T, gap, ins */
+} ccsx_pileup;
+int ccsx_gpu_set_pileup(ccsx_ctx *ctx, int on);
+int ccsx_gpu_pileup(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_pileup **p, uint32_t *len);
 /* The same in three steps (one slice, tight capacities, no re-run), so inputs
  * can stay resident in HBM across launches (used by bench.py).
  * ccsx_gpu_launch returns the kernel time measured with HIP events on the
@@ -205,7 +238,8 @@ int ccsx_gpu_launch(ccsx_ctx *ctx, int mode, float *kernel_ms);
 int ccsx_gpu_fetch(ccsx_ctx *ctx, ccsx_zmw_out *out);
 
 /* Device bytes the staged batch occupies (workspace + arenas; the quality
- * plane, the pass records and the base map when the batch has them). */
+ * plane, the pass records, the base map and the strand pileup with its strand
+ * flags when the batch has them). */
 uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *ctx);
 
 /* Diagnostics: per-phase shader-clock counters (s_memtime) summed over the
@@ -265,7 +299,8 @@ int ccsx_gpu_set_mem_wait(ccsx_ctx *ctx, uint32_t ms);
 /* Device bytes ZMW *z occupies in a ccsx_gpu_run slice of `mode` (tight
  * capacities: workspace, subreads, output slab -- twice with quality on --,
  * tables, 24 bytes per segment with pass statistics on, 4 bytes per pushed
- * base with the base map on). */
+ * base with the base map on, 12 bytes per output slab byte and one per segment
+ * with the strand pileup on). */
 uint64_t ccsx_gpu_zmw_bytes(const ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z);
 /* Test hook: bytes per slot for ccsx_gpu_run's slices (0 = by device memory:
  * half of this context's share, ccsx_gpu_set_mem_share), so a small batch is

@@ -84,6 +84,16 @@ typedef struct {
 } ccsx_map_aln;
 long ccsx_map_cigar(const uint32_t *map, uint32_t len, ccsx_map_aln *aln, char *cigar, size_t cap);
 
+/* The call of one strand at a CCS position from its pileup record (SPEC.md
+ * section 12; records from ccsx_gpu_pileup): strand 0 = the forward reads'
+ * counts, 1 = the reverse reads', 2 = both (the fieldwise sum of the stored
+ * bytes).  The column rule on that strand's five counts A, C, G, T, gap: -1 if
+ * they sum to 0; else best = the base with the largest count (ties: the
+ * smallest), and the call is best (0 .. 3) if its count >= gap, else 4 (gap).
+ * A position whose forward and reverse calls are both >= 0 and differ is a
+ * discordant site.  -1 also for p == NULL or another strand value. */
+int ccsx_pileup_call(const ccsx_pileup *p, int strand);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
@@ -96,7 +106,8 @@ uint64_t ccsx_synth_zmw(uint64_t seed, uint64_t hole, uint32_t L, uint32_t passe
 /* Benchmarks: n synthetic ZMWs (ccsx_synth_zmw(seed, holes[i], L[i],
  * passes[i]), then ccsx_prepare_apply) made on nthreads threads; the batch
  * owns the data, ccsx_synth_batch_zmws gives the n push lists
- * (ccsx_zmw_in, include/ccsx_gpu.h) ready for ccsx_gpu_run. */
+ * (ccsx_zmw_in, include/ccsx_gpu.h; seg_rev = ccsx_prepare's flags) ready for
+ * ccsx_gpu_run. */
 typedef struct ccsx_synth_batch ccsx_synth_batch;
 ccsx_synth_batch *ccsx_synth_batch_make(uint64_t seed, const uint64_t *holes, const uint32_t *L,
                                         const uint32_t *passes, uint32_t n, int nthreads);
