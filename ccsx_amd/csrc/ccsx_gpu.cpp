@@ -4,6 +4,11 @@
 // descriptor and one workspace slab per ZMW, laid out by ccsx_layout.h),
 // launches one workgroup per ZMW and copies the CCS strings back; slices of
 // a large chunk alternate between two slots (streams) so they overlap.
+// The optional per-ZMW outputs beside the CCS (qualities, pass records, map,
+// pileup) are described once, in side_out.h: their sizes, their planes in a
+// fetched slice, the container a batch's results are gathered into and the
+// accessors' lookup; here they are a mask, loops over it, and their wiring
+// into the kernel's arguments (launch_slot).
 // This is the device boundary that replaces kt_for(ccs_for2/ccs_for) in step 1
 // of ccsx's pipeline (main.c:698-706).
 #include "ccsx_gpu.h"
@@ -21,6 +26,7 @@
 #include <vector>
 
 #include "ccsx_layout.h"
+#include "side_out.h"
 
 // the kernel configurations (ccsx_layout.h KernelCfg), one object each: the
 // launcher and the configuration's own LDS / thread figures
@@ -39,18 +45,16 @@ extern "C" void ccsx_kcfg_info_solo16w(ccsx::KCfgInfo *o);
 
 namespace {
 typedef hipError_t (*LaunchFn)(const ccsx::KArgs *, uint32_t, hipStream_t);
+typedef void (*InfoFn)(ccsx::KCfgInfo *);
 constexpr LaunchFn kLaunch[ccsx::kCfgCount] = {ccsx_launch_zmw_lat,  ccsx_launch_zmw_occ,    ccsx_launch_zmw_tput,
                                                ccsx_launch_zmw_solo, ccsx_launch_zmw_solo16, ccsx_launch_zmw_solo16w};
+constexpr InfoFn kInfo[ccsx::kCfgCount] = {ccsx_kcfg_info_lat,  ccsx_kcfg_info_occ,    ccsx_kcfg_info_tput,
+                                           ccsx_kcfg_info_solo, ccsx_kcfg_info_solo16, ccsx_kcfg_info_solo16w};
 
 ccsx::KCfgInfo kcfg_info(int cfg)
 {
     ccsx::KCfgInfo o{};
-    if (cfg == ccsx::kCfgLatency) ccsx_kcfg_info_lat(&o);
-    else if (cfg == ccsx::kCfgOccupancy) ccsx_kcfg_info_occ(&o);
-    else if (cfg == ccsx::kCfgThroughput) ccsx_kcfg_info_tput(&o);
-    else if (cfg == ccsx::kCfgSolo) ccsx_kcfg_info_solo(&o);
-    else if (cfg == ccsx::kCfgSolo16) ccsx_kcfg_info_solo16(&o);
-    else ccsx_kcfg_info_solo16w(&o);
+    kInfo[cfg](&o);
     return o;
 }
 
@@ -172,86 +176,6 @@ struct DevBuf {
     }
 };
 
-
-// The gathered pass records (SPEC.md §10) of one ccsx_gpu_run call or one
-// collected batch, per ZMW of the call in input order
-struct PassSet {
-    std::vector<uint32_t> words;   // kPassWords per segment
-    std::vector<uint64_t> off;     // per ZMW: word offset into words
-    std::vector<uint32_t> nseg;    // per ZMW: records
-    std::vector<uint8_t> ok;       // per ZMW: it has a result (status 0)
-    void reset(size_t nz)
-    {
-        words.clear();
-        off.assign(nz, 0);
-        nseg.assign(nz, 0);
-        ok.assign(nz, 0);
-    }
-    void put(size_t g, const uint32_t *rec, uint32_t n)
-    {
-        off[g] = words.size();
-        nseg[g] = n;
-        ok[g] = 1;
-        words.insert(words.end(), rec, rec + size_t(n) * ccsx::kPassWords);
-    }
-};
-
-// The gathered subread-to-CCS maps (SPEC.md §11) of one ccsx_gpu_run call or
-// one collected batch, per ZMW of the call in input order
-struct MapSet {
-    std::vector<uint32_t> words;   // a word per pushed base, a ZMW's segments back to back
-    std::vector<uint64_t> spos;    // per gathered segment: word offset into words
-    std::vector<uint32_t> slen;    // per gathered segment: entries
-    std::vector<uint64_t> seg0;    // per ZMW: its first segment in spos / slen
-    std::vector<uint32_t> nseg;    // per ZMW: segments
-    std::vector<uint8_t> ok;       // per ZMW: it has a result (status 0)
-    void reset(size_t nz)
-    {
-        words.clear();
-        spos.clear();
-        slen.clear();
-        seg0.assign(nz, 0);
-        nseg.assign(nz, 0);
-        ok.assign(nz, 0);
-    }
-    void put(size_t g, const uint32_t *map, const uint32_t *len, uint32_t n)
-    {
-        seg0[g] = spos.size();
-        nseg[g] = n;
-        ok[g] = 1;
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < n; ++k) {
-            spos.push_back(words.size() + tot);
-            slen.push_back(len[k]);
-            tot += len[k];
-        }
-        words.insert(words.end(), map, map + tot);
-    }
-};
-
-// The gathered strand pileups (SPEC.md §12) of one ccsx_gpu_run call or one
-// collected batch, per ZMW of the call in input order
-struct PileSet {
-    std::vector<ccsx_pileup> recs;  // a record per CCS base, the ZMWs back to back
-    std::vector<uint64_t> off;      // per ZMW: record offset into recs
-    std::vector<uint32_t> len;      // per ZMW: records (= its CCS length)
-    std::vector<uint8_t> ok;        // per ZMW: it has a result (status 0)
-    void reset(size_t nz)
-    {
-        recs.clear();
-        off.assign(nz, 0);
-        len.assign(nz, 0);
-        ok.assign(nz, 0);
-    }
-    void put(size_t g, const ccsx_pileup *rec, uint32_t n)
-    {
-        off[g] = recs.size();
-        len[g] = n;
-        ok[g] = 1;
-        recs.insert(recs.end(), rec, rec + n);
-    }
-};
-
 // One staged slice and everything it owns on the device and the host.  A
 // context has two: ccsx_gpu_run stages and launches slice k + 1 on the other
 // slot's stream while slice k's kernel runs, so one slice's tail (the launch
@@ -267,49 +191,30 @@ struct Slot {
     uint64_t seq_bytes = 0, ws_bytes = 0, out_bytes = 0, msa_bytes = 0, bp_words = 0;
     uint32_t nseg_total = 0;
     bool inflight = false;             // launched, results not fetched yet
-    // staged with a quality plane (ccsx_gpu_set_quality): out_bytes more behind
-    // the CCS plane in d_out and h_out, a byte per CCS byte at the same offsets
-    bool qual = false;
-    // staged with pass records (ccsx_gpu_set_pass_stats): kPassWords words per
-    // segment in d_pstat; in h_out at pst_off(), behind the plane(s)
-    bool pstat = false;
-    uint64_t pst_off() const { return (out_bytes * (qual ? 2 : 1) + 7) & ~uint64_t(7); }
-    uint64_t pst_bytes() const { return pstat ? uint64_t(nseg_total) * ccsx::kPassWords * 4 : 0; }
-    const uint32_t *h_pstat(size_t zmw) const
-    {
-        return reinterpret_cast<const uint32_t *>(h_out.p + pst_off()) + size_t(desc[zmw].seg0) * ccsx::kPassWords;
-    }
-    // staged with the subread-to-CCS map (ccsx_gpu_set_base_map): a word per
-    // pushed base in d_bmap, ZMW i's segments back to back at word hbmoff[i]
-    // (d_bmoff; its 8 bytes per ZMW lie within the 32 that every size counts
-    // for a ZMW's tables); in h_out at bm_off(), behind the pass records
-    bool bmap = false;
+    // the optional outputs it was staged with (side_out.h) and where their
+    // planes lie in h_out: the quality plane behind the CCS plane in d_out, a
+    // byte per CCS byte at the same offsets; kPassWords words per segment in
+    // d_side[kSidePass]; a map word per pushed base in d_side[kSideMap], ZMW
+    // i's segments back to back at word hbmoff[i] (d_bmoff; its 8 bytes per
+    // ZMW lie within the 32 that every size counts for a ZMW's tables);
+    // kPuBytes per byte of the output slab in d_side[kSidePile], the record of
+    // a base at its slab offset, and a strand flag per segment in d_srev
+    // (hsrev: the host copy, the index space of hlen)
+    ccsx::SideLayout lay;
     uint64_t nbase_total = 0;          // pushed bases of the slice
-    uint64_t bm_off() const { return ((pstat ? pst_off() + pst_bytes() : out_bytes * (qual ? 2 : 1)) + 7) & ~uint64_t(7); }
-    uint64_t bm_bytes() const { return bmap ? nbase_total * 4 : 0; }
-    const uint32_t *h_bmap(size_t zmw) const { return reinterpret_cast<const uint32_t *>(h_out.p + bm_off()) + hbmoff[zmw]; }
     std::vector<uint64_t> hbmoff;
-    // staged with the strand pileup (ccsx_gpu_set_pileup): kPuBytes per byte of
-    // the output slab in d_pile, the record of a base at its slab offset, and a
-    // strand flag per segment in d_srev (hsrev: the host copy, the index space of
-    // hlen); in h_out at pu_off(), behind the map, the flags behind the records
-    bool pile = false;
-    uint64_t pu_off() const
-    {
-        return ((bmap ? bm_off() + bm_bytes() : pstat ? pst_off() + pst_bytes() : out_bytes * (qual ? 2 : 1)) + 7) & ~uint64_t(7);
-    }
-    uint64_t pu_bytes() const { return pile ? out_bytes * ccsx::kPuBytes : 0; }
-    uint64_t srev_bytes() const { return pile ? uint64_t(nseg_total) : 0; }
-    const ccsx_pileup *h_pile(size_t zmw) const
-    {
-        return reinterpret_cast<const ccsx_pileup *>(h_out.p + pu_off()) + desc[zmw].out_off;
-    }
     std::vector<uint8_t> hsrev;
+    // the fetched slice as the gathering and the accessors read it
+    ccsx::SideView view() const
+    {
+        return {&lay, h_out.p, nz, desc.data(), hlen.data(), hbmoff.data(), h_status.data(), h_olen.data()};
+    }
     std::vector<ccsx::ZmwDesc> desc;
     std::vector<uint32_t> hoff, hlen, order;  // host copies the async H2D reads from
     DevBuf d_prof, d_bp;
-    DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells, d_pstat;
-    DevBuf d_bmap, d_bmoff, d_pile, d_srev;
+    DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells;
+    DevBuf d_side[ccsx::kSideCount];   // the planes with a buffer of their own (not SideInfo::in_out)
+    DevBuf d_bmoff, d_srev;
     HostBuf h_out, h_seq;
     std::vector<uint32_t> h_olen, h_ncols, h_bp;
     std::vector<int32_t> h_status;
@@ -318,8 +223,9 @@ struct Slot {
     void release()
     {
         DevBuf *bufs[] = {&d_bp, &d_prof, &d_seq, &d_soff, &d_slen, &d_desc, &d_order, &d_ws, &d_out,
-                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_pstat, &d_bmap, &d_bmoff, &d_pile, &d_srev};
+                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_bmoff, &d_srev};
         for (DevBuf *b : bufs) b->release();
+        for (DevBuf &b : d_side) b.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         for (hipEvent_t &e : evp)
@@ -367,50 +273,23 @@ struct ccsx_ctx {
     uint64_t mem_waits = 0, mem_replans = 0;  // slices that waited for memory / were cut below the plan
     bool prealloc = false;             // reserve the slice budget up front
     bool bp_log = false;               // record the -v >= 3 breakpoint log (main.c:619-620)
-    bool quality = false;              // stage a quality plane beside the CCS (ccsx_gpu_set_quality)
-    // ccsx_gpu_quality(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
-    int last_qual = 0;
-    std::vector<uint8_t> run_qual;     // ccsx_gpu_run's gathered qualities (run_arena's offsets)
-    std::vector<uint64_t> run_qoff;    // per ZMW of the call: offset into run_qual
-    std::vector<uint32_t> run_qlen;    // per ZMW of the call: quality bytes (0: no CCS)
-    bool pass_stats = false;           // stage pass records beside the CCS (ccsx_gpu_set_pass_stats)
-    // ccsx_gpu_pass_stats(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
-    int last_pst = 0;
-    PassSet run_pst;                   // ccsx_gpu_run's gathered pass records
-    bool base_map = false;             // stage the subread-to-CCS map beside the CCS (ccsx_gpu_set_base_map)
-    // ccsx_gpu_base_map(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
-    int last_bm = 0;
-    MapSet run_bm;                     // ccsx_gpu_run's gathered maps
-    bool pileup = false;               // stage the strand pileup beside the CCS (ccsx_gpu_set_pileup)
-    // ccsx_gpu_pileup(slot = -1): what the last ccsx_gpu_run (1) / ccsx_gpu_fetch (2) left
-    int last_pu = 0;
-    PileSet run_pu;                    // ccsx_gpu_run's gathered pileups
+    ccsx::SideMask side = 0;           // the optional outputs staged beside the CCS (ccsx_gpu_set_quality, ...)
+    // the accessors' slot = -1: what the last ccsx_gpu_run (1: run) / ccsx_gpu_fetch (2: slot 0) left
+    int last = 0;
+    ccsx::Gathered run;                // ccsx_gpu_run's gathered CCS strings and outputs
     std::vector<uint32_t> run_bp;      // ccsx_gpu_run: the gathered logs, (i, ncols) pairs
     std::vector<uint64_t> run_bp_off;  // per ZMW of the call: offset into run_bp (pairs)
     std::vector<uint32_t> run_bp_n;    // per ZMW of the call: rounds
-    std::vector<uint8_t> run_arena;    // ccsx_gpu_run's gathered CCS strings
     // ccsx_gpu_submit / ccsx_gpu_collect: one batch per slot
     struct Ticket {
         bool pending = false;          // submitted, not collected
+        bool collected = false;        // collected, and res holds its results
         int mode = 0;
         const ccsx_zmw_in *z = nullptr;  // the caller's batch (valid until collected)
         size_t nz = 0;
         int64_t fault = -1;            // test hook, taken from ccsx_gpu_set_fault at submit
-        std::vector<uint8_t> arena;    // the collected batch's CCS strings
-        bool qual = false;             // submitted with quality on
-        bool has_qual = false;         // collected, and qarena / qoff / qlen hold its qualities
-        std::vector<uint8_t> qarena;   // the collected batch's qualities (arena's offsets)
-        std::vector<uint64_t> qoff;
-        std::vector<uint32_t> qlen;
-        bool pstat = false;            // submitted with pass statistics on
-        bool has_pst = false;          // collected, and pst holds its pass records
-        PassSet pst;
-        bool bmap = false;             // submitted with the subread-to-CCS map on
-        bool has_bm = false;           // collected, and bm holds its maps
-        MapSet bm;
-        bool pile = false;             // submitted with the strand pileup on
-        bool has_pu = false;           // collected, and pu holds its pileups
-        PileSet pu;
+        ccsx::SideMask side = 0;       // the outputs it was submitted with
+        ccsx::Gathered res;            // the collected batch
     } tk[2];
 };
 
@@ -551,6 +430,10 @@ static void zmw_extent(const ccsx_zmw_in &zi, uint64_t &S, uint64_t &hi, uint32_
     }
 }
 
+// the LDS read buffer cap of tight-cap slices, bases: shred_read_cap in a
+// shredded call, none otherwise
+static uint32_t shred_win(const ccsx_ctx *c) { return c->shred_caps ? c->shred_read_cap : 0u; }
+
 // device bytes one ZMW occupies when staged
 static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, uint32_t shred_win)
 {
@@ -561,9 +444,8 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::zcaps(d, S, lmax, zi.nseg, full, c->tight_rows, shred_win, c->tight_out, c->tight_far);
     ccsx::ZLayout L;
     ccsx::zlayout(L, d);
-    return ccsx::align256(L.total) + hi + d.outcap + (c->quality ? d.outcap : 0u) + uint64_t(zi.nseg) * 8 +
-           (c->pass_stats ? uint64_t(zi.nseg) * ccsx::kPassWords * 4 : 0u) + (c->base_map ? S * 4 : 0u) +
-           (c->pileup ? uint64_t(d.outcap) * ccsx::kPuBytes + zi.nseg : 0u) + sizeof(ccsx::ZmwDesc) + 32;
+    return ccsx::align256(L.total) + hi + d.outcap + ccsx::side_bytes_of(c->side, d.outcap, zi.nseg, S) +
+           uint64_t(zi.nseg) * 8 + sizeof(ccsx::ZmwDesc) + 32;
 }
 
 // The bytes a slice staged into slot s may need now: the device's free memory
@@ -576,7 +458,8 @@ static int slot_avail(ccsx_ctx *c, const Slot &s, uint64_t &avail)
 {
     size_t freeb = 0, totb = 0;
     HIPCHK(c, hipMemGetInfo(&freeb, &totb));
-    const uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap + s.d_pstat.cap + s.d_bmap.cap + s.d_pile.cap;
+    uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap;
+    for (const DevBuf &b : s.d_side) have += b.cap;
     avail = have > (1ull << 30) ? have - (1ull << 30) : 0;
     return 0;
 }
@@ -617,8 +500,9 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     s.desc.assign(nz, ccsx::ZmwDesc{});
     uint64_t seq_b = 0, ws_b = 0, out_b = 0, msa_b = 0, bp_w = 0, nbase = 0;
     uint32_t nseg = 0, lmax_all = 0, nmax = 0;
-    s.bmap = c->base_map && !with_msa;
-    s.hbmoff.resize(s.bmap ? nz : 0);
+    const ccsx::SideMask side = with_msa ? 0 : c->side;
+    const bool with_map = (side & ccsx::side_bit(ccsx::kSideMap)) != 0;
+    s.hbmoff.resize(with_map ? nz : 0);
     for (size_t i = 0; i < nz; ++i) {
         const ccsx_zmw_in &zi = z[i];
         uint64_t S, hi;
@@ -629,8 +513,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
             return -1;
         }
         ccsx::ZmwDesc &d = s.desc[i];
-        ccsx::zcaps(d, S, lmax, zi.nseg, full_caps != 0, c->tight_rows, c->shred_caps ? c->shred_read_cap : 0u,
-                    c->tight_out, c->tight_far);
+        ccsx::zcaps(d, S, lmax, zi.nseg, full_caps != 0, c->tight_rows, shred_win(c), c->tight_out, c->tight_far);
         d.seg0 = nseg;
         d.seq_off = seq_b;
         seq_b += hi;
@@ -649,7 +532,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         d.bpcap = c->bp_log ? (full_caps ? uint32_t(S + 2) : uint32_t(S / 512 + 64)) : 0u;
         d.bp_off = bp_w;
         bp_w += c->bp_log ? 1 + 2 * uint64_t(d.bpcap) : 0;
-        if (s.bmap) s.hbmoff[i] = nbase;
+        if (with_map) s.hbmoff[i] = nbase;
         nbase += S;
         nseg += zi.nseg;
         lmax_all = std::max(lmax_all, lmax);
@@ -659,13 +542,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     s.seq_bytes = seq_b, s.ws_bytes = ws_b, s.out_bytes = out_b, s.msa_bytes = msa_b;
     s.bp_words = bp_w;
     s.nseg_total = nseg;
-    s.qual = c->quality && !with_msa;
-    const uint64_t qual_b = s.qual ? out_b : 0;
-    s.pstat = c->pass_stats && !with_msa;
-    const uint64_t pst_b = s.pst_bytes();
-    const uint64_t bm_b = s.bm_bytes();
-    s.pile = c->pileup && !with_msa;
-    const uint64_t pu_b = s.pu_bytes() + s.srev_bytes();
+    s.lay.plan(side, out_b, nseg, nbase);
     // 2-bit read buffer (ccsx_kernel.hip stage_read); at least one band:
     // every lane reads its window bytes even when the read is shorter.  A
     // slice with a read or a cursor array beyond the LDS budget runs the
@@ -721,8 +598,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + qual_b + pst_b + bm_b + pu_b + msa_b + bp_w * 4 + uint64_t(nseg) * 8 +
-                          nz * (sizeof(ccsx::ZmwDesc) + 32);
+    const uint64_t need = seq_b + ws_b + out_b + ccsx::side_bytes_of(side, out_b, nseg, nbase) + msa_b + bp_w * 4 +
+                          uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
         // already cut the slice to what is free; a submitted batch cannot be cut)
@@ -748,16 +625,11 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, s.d_desc.reserve(nz * sizeof(ccsx::ZmwDesc)));
     HIPCHK(c, s.d_order.reserve(nz * 4));
     HIPCHK(c, s.d_ws.reserve(ws_b));
-    HIPCHK(c, s.d_out.reserve(out_b + qual_b));
-    if (pst_b) HIPCHK(c, s.d_pstat.reserve(pst_b));
-    if (s.bmap) {
-        HIPCHK(c, s.d_bmap.reserve(bm_b));
-        HIPCHK(c, s.d_bmoff.reserve(nz * 8));
-    }
-    if (s.pile) {
-        HIPCHK(c, s.d_pile.reserve(s.pu_bytes()));
-        HIPCHK(c, s.d_srev.reserve(s.srev_bytes()));
-    }
+    HIPCHK(c, s.d_out.reserve(s.lay.out_dev));
+    for (int o = 0; o < ccsx::kSideCount; ++o)
+        if (!ccsx::kSide[o].in_out) HIPCHK(c, s.d_side[o].reserve(s.lay.plane[o]));
+    if (with_map) HIPCHK(c, s.d_bmoff.reserve(nz * 8));
+    if (s.lay.has(ccsx::kSidePile)) HIPCHK(c, s.d_srev.reserve(nseg));
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
     HIPCHK(c, s.d_ncols.reserve(nz * 4));
@@ -844,8 +716,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, hipMemcpyAsync(s.d_soff.p, s.hoff.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_slen.p, s.hlen.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_desc.p, s.desc.data(), nz * sizeof(ccsx::ZmwDesc), hipMemcpyHostToDevice, s.stream));
-    if (s.bmap && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
-    if (s.pile) {
+    if (with_map && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
+    if (s.lay.has(ccsx::kSidePile)) {
         // the strand flags, read only here: a ZMW without them is all forward
         s.hsrev.assign(nseg, 0);
         for (size_t i = 0; i < nz; ++i)
@@ -892,14 +764,16 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     if (!s.lds_read_words) ++c->hbm_launches;
     a.prof = nullptr;
     a.bplog = s.bp_words ? s.d_bp.as<uint32_t>() : nullptr;
-    a.qual = s.qual ? s.d_out.as<uint8_t>() + s.out_bytes : nullptr;
-    a.pstat = s.pst_bytes() ? s.d_pstat.as<uint32_t>() : nullptr;
-    // (a slice without a pushed base has no map to write: the feature-off kernels run it)
-    a.bmap = s.bm_bytes() ? s.d_bmap.as<uint32_t>() : nullptr;
-    a.bmoff = s.bm_bytes() ? s.d_bmoff.as<uint64_t>() : nullptr;
-    // (likewise a slice without an output byte has no record to write)
-    a.pile = s.pu_bytes() ? s.d_pile.as<uint8_t>() : nullptr;
-    a.srev = s.pu_bytes() && s.srev_bytes() ? s.d_srev.as<uint8_t>() : nullptr;
+    // the optional outputs: a plane without a byte (a slice without a segment,
+    // a pushed base or an output byte) has nothing to write, and the
+    // feature-off kernels run it
+    const ccsx::SideLayout &L = s.lay;
+    a.qual = L.has(ccsx::kSideQual) ? s.d_out.as<uint8_t>() + L.off[ccsx::kSideQual] : nullptr;
+    a.pstat = L.plane[ccsx::kSidePass] ? s.d_side[ccsx::kSidePass].as<uint32_t>() : nullptr;
+    a.bmap = L.plane[ccsx::kSideMap] ? s.d_side[ccsx::kSideMap].as<uint32_t>() : nullptr;
+    a.bmoff = L.plane[ccsx::kSideMap] ? s.d_bmoff.as<uint64_t>() : nullptr;
+    a.pile = L.plane[ccsx::kSidePile] ? s.d_side[ccsx::kSidePile].as<uint8_t>() : nullptr;
+    a.srev = L.plane[ccsx::kSidePile] && s.nseg_total ? s.d_srev.as<uint8_t>() : nullptr;
     if (c->profiling) {
         HIPCHK(c, s.d_prof.reserve(s.nz * ccsx::kProfSlots * 8));
         a.prof = s.d_prof.as<unsigned long long>();
@@ -923,15 +797,8 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
 {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nz = s.nz;
-    const uint64_t planes = s.qual ? 2 : 1;  // the quality plane follows the CCS plane, one copy for both
-    // (the pass records follow the planes, 8-byte aligned)
-    // (and the map follows those, 8-byte aligned, and the pileup records with
-    // the strand flags behind them follow that, 8-byte aligned)
-    HIPCHK(c, s.h_out.reserve(s.pile    ? s.pu_off() + s.pu_bytes() + s.srev_bytes()
-                              : s.bmap  ? s.bm_off() + s.bm_bytes()
-                              : s.pstat ? s.pst_off() + s.pst_bytes()
-                                        : s.out_bytes * planes,
-                              c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
+    const ccsx::SideLayout &L = s.lay;
+    HIPCHK(c, s.h_out.reserve(L.total, c->prealloc ? kPinnedOutFloor / c->mem_share : 0));
     s.h_olen.resize(nz);
     s.h_status.resize(nz);
     s.h_cells.resize(nz);
@@ -940,16 +807,16 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
         HIPCHK(c, hipMemcpyAsync(s.h_olen.data(), s.d_olen.p, nz * 4, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipMemcpyAsync(s.h_status.data(), s.d_status.p, nz * 4, hipMemcpyDeviceToHost, s.stream));
         HIPCHK(c, hipMemcpyAsync(s.h_cells.data(), s.d_cells.p, nz * 8, hipMemcpyDeviceToHost, s.stream));
-        HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, s.out_bytes * planes, hipMemcpyDeviceToHost, s.stream));
-        if (s.pst_bytes())
-            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pst_off(), s.d_pstat.p, s.pst_bytes(), hipMemcpyDeviceToHost, s.stream));
-        if (s.bm_bytes())
-            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.bm_off(), s.d_bmap.p, s.bm_bytes(), hipMemcpyDeviceToHost, s.stream));
-        if (s.pu_bytes())
-            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pu_off(), s.d_pile.p, s.pu_bytes(), hipMemcpyDeviceToHost, s.stream));
-        if (s.pu_bytes() && s.srev_bytes())
-            HIPCHK(c, hipMemcpyAsync(s.h_out.p + s.pu_off() + s.pu_bytes(), s.d_srev.p, s.srev_bytes(), hipMemcpyDeviceToHost,
-                                     s.stream));
+        // the CCS plane and the plane behind it in one copy, then the planes with buffers of their own
+        HIPCHK(c, hipMemcpyAsync(s.h_out.p, s.d_out.p, L.out_dev, hipMemcpyDeviceToHost, s.stream));
+        for (int o = 0; o < ccsx::kSideCount; ++o) {
+            if (ccsx::kSide[o].in_out || !L.plane[o]) continue;
+            HIPCHK(c, hipMemcpyAsync(s.h_out.p + L.off[o], s.d_side[o].p, L.plane[o], hipMemcpyDeviceToHost, s.stream));
+            // (its flags, the pileup's strand flags, behind it)
+            if (L.bytes[o] > L.plane[o])
+                HIPCHK(c, hipMemcpyAsync(s.h_out.p + L.off[o] + L.plane[o], s.d_srev.p, L.bytes[o] - L.plane[o],
+                                         hipMemcpyDeviceToHost, s.stream));
+        }
         if (s.bp_words)
             HIPCHK(c, hipMemcpyAsync(s.h_bp.data(), s.d_bp.p, s.bp_words * 4, hipMemcpyDeviceToHost, s.stream));
     }
@@ -984,10 +851,7 @@ int ccsx_gpu_stage_ex(ccsx_ctx *c, const ccsx_zmw_in *z, size_t nz, int with_msa
         HIPCHK(c, hipStreamSynchronize(s.stream));
         s.inflight = false;
     }
-    c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
-    c->last_pst = 0;
-    c->last_bm = 0;
-    c->last_pu = 0;
+    c->last = 0;  // (slot 0's fetched results go with its arenas)
     const int r = stage_slot(c, s, z, nz, with_msa, full_caps);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(s.stream));
@@ -1038,12 +902,9 @@ int ccsx_gpu_launch(ccsx_ctx *c, int mode, float *kernel_ms)
 int ccsx_gpu_fetch(ccsx_ctx *c, ccsx_zmw_out *out)
 {
     if (!c) return -1;
-    c->last_qual = 0;
-    c->last_pst = 0;
-    c->last_bm = 0;
-    c->last_pu = 0;
+    c->last = 0;
     const int r = fetch_slot(c, c->slot[0], out);
-    if (r == 0 || r == -2) c->last_qual = c->last_pst = c->last_bm = c->last_pu = 2;
+    if (r == 0 || r == -2) c->last = 2;
     return r;
 }
 
@@ -1098,6 +959,45 @@ static bool is_cap_error(int32_t s)
            s == ccsx::kErrReadLen || s == ccsx::kErrBpLog || s == ccsx::kErrOut;
 }
 
+// Gather the fetched slice of slot s into `to` and the caller's out[]: ZMW i of
+// the slice (res[i]) is input idx[i] of the call (idx null: i).  A ZMW that outgrew a tight
+// cap goes to `retry` (null: the slice ran with full caps); the first other
+// failure is kept in first_err.
+static void gather_slice(const Slot &s, const ccsx_zmw_out *res, const uint32_t *idx, ccsx::Gathered &to,
+                         ccsx_zmw_out *out, std::vector<uint32_t> *retry, std::string &first_err)
+{
+    size_t add = 0;
+    for (size_t i = 0; i < s.nz; ++i) add += res[i].len;
+    to.grow(add);
+    const ccsx::SideView v = s.view();
+    for (size_t i = 0; i < s.nz; ++i) {
+        const uint32_t g = idx ? idx[i] : uint32_t(i);
+        out[g].cells = res[i].cells;
+        out[g].status = res[i].status;
+        out[g].len = res[i].len;
+        if (!res[i].status) {
+            to.put(g, v.rec(i));
+        } else if (retry && is_cap_error(res[i].status)) {
+            retry->push_back(g);
+        } else if (first_err.empty()) {
+            char m[200];
+            snprintf(m, sizeof m, "ZMW %u of the batch failed on the device: %s", g, ccsx_gpu_status_str(res[i].status));
+            first_err = m;
+        }
+    }
+}
+
+// The test hook's fault (ccsx_gpu_set_fault): ZMW `fault` of the call is
+// reported as failed after all, without a result in every output
+static void inject_fault(int64_t fault, ccsx::Gathered &to, ccsx_zmw_out *out, std::string &first_err)
+{
+    if (fault < 0 || (size_t)fault >= to.size()) return;
+    out[fault].status = ccsx::kErrTrace;
+    out[fault].len = 0;
+    to.drop(fault);
+    if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
+}
+
 // One chunk.  The chunk is cut into slices that fit the device's free memory
 // (tight caps); a ZMW that outgrows a tight cap is re-run with full caps.
 // Slices alternate between the context's two slots: slice k + 1 is staged and
@@ -1130,21 +1030,11 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
     const bool timing = getenv("CCSX_TIMING") && atoi(getenv("CCSX_TIMING"));
     using ms = std::chrono::duration<double, std::milli>;
     const auto t_run = std::chrono::steady_clock::now();
-    c->run_arena.clear();
-    c->last_qual = 0;
-    c->run_qual.clear();
-    c->run_qoff.assign(c->quality ? nz : 0, 0);
-    c->run_qlen.assign(c->quality ? nz : 0, 0);
-    c->last_pst = 0;
-    c->run_pst.reset(c->pass_stats ? nz : 0);
-    c->last_bm = 0;
-    c->run_bm.reset(c->base_map ? nz : 0);
-    c->last_pu = 0;
-    c->run_pu.reset(c->pileup ? nz : 0);
+    c->last = 0;
+    c->run.reset(nz, c->side);
     c->run_bp.clear();
     c->run_bp_off.assign(nz, 0);
     c->run_bp_n.assign(nz, 0);
-    std::vector<uint64_t> aoff(nz, 0);
     std::vector<int> cls(nz, 0);
     std::string first_err;
     // results of the slice in slot s (input indices idx[b, b + s.nz))
@@ -1169,49 +1059,16 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
                     ms(std::chrono::steady_clock::now() - t_run).count());
         }
         const Pending &p = pend[si];
-        {
-            // one growth of the gathered CCS arena per slice, not one per
-            // ZMW's append (~150 MB for a 10k-ZMW config-E slice)
-            size_t add = 0;
-            for (size_t i = 0; i < s.nz; ++i) add += o[i].status ? 0 : o[i].len;
-            c->run_arena.reserve(c->run_arena.size() + add);
-            if (s.qual) c->run_qual.reserve(c->run_qual.size() + add);
-        }
-        for (size_t i = 0; i < s.nz; ++i) {
-            const uint32_t g = (*p.idx)[p.b + i];
-            out[g].cells = o[i].cells;
-            out[g].status = o[i].status;
-            out[g].len = 0;
-            if (o[i].status) {
-                if (p.retry && is_cap_error(o[i].status)) {
-                    p.retry->push_back(g);
-                } else if (first_err.empty()) {
-                    char m[200];
-                    snprintf(m, sizeof m, "ZMW %u of the batch failed on the device: %s", g,
-                             ccsx_gpu_status_str(o[i].status));
-                    first_err = m;
-                }
-                continue;
-            }
-            aoff[g] = c->run_arena.size();
-            out[g].len = o[i].len;
-            c->run_arena.insert(c->run_arena.end(), o[i].ccs, o[i].ccs + o[i].len);
-            if (s.qual) {
-                const uint8_t *q = s.h_out.p + s.out_bytes + s.desc[i].out_off;
-                c->run_qoff[g] = c->run_qual.size();
-                c->run_qlen[g] = o[i].len;
-                c->run_qual.insert(c->run_qual.end(), q, q + o[i].len);
-            }
-            if (s.pstat) c->run_pst.put(g, s.h_pstat(i), s.desc[i].n);
-            if (s.bmap) c->run_bm.put(g, s.h_bmap(i), s.hlen.data() + s.desc[i].seg0, s.desc[i].n);
-            if (s.pile) c->run_pu.put(g, s.h_pile(i), o[i].len);
-            if (s.bp_words && mode == CCSX_MODE_SHRED) {
+        gather_slice(s, o.data(), p.idx->data() + p.b, c->run, out, p.retry, first_err);
+        if (s.bp_words && mode == CCSX_MODE_SHRED)
+            for (size_t i = 0; i < s.nz; ++i) {
+                if (o[i].status) continue;
+                const uint32_t g = (*p.idx)[p.b + i];
                 const uint32_t *lg = s.h_bp.data() + s.desc[i].bp_off;
                 c->run_bp_off[g] = c->run_bp.size() / 2;
                 c->run_bp_n[g] = lg[0];
                 c->run_bp.insert(c->run_bp.end(), lg + 1, lg + 1 + 2 * uint64_t(lg[0]));
             }
-        }
         return 0;
     };
     int next_slot = 0;
@@ -1236,7 +1093,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             std::vector<uint64_t> xb(idx0.size());
             uint64_t tot = 0, xmax = 0;
             for (size_t i = 0; i < idx0.size(); ++i) {
-                xb[i] = zmw_bytes(z[idx0[i]], full, c, c->shred_caps ? c->shred_read_cap : 0u);
+                xb[i] = zmw_bytes(z[idx0[i]], full, c, shred_win(c));
                 tot += xb[i];
                 xmax = std::max(xmax, xb[i]);
             }
@@ -1277,7 +1134,7 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             {
                 uint64_t avail = 0;
                 if ((r = slot_avail(c, c->slot[si], avail))) return r;
-                const uint64_t x0 = zmw_bytes(z[idx[b]], full, c, c->shred_caps ? c->shred_read_cap : 0u);
+                const uint64_t x0 = zmw_bytes(z[idx[b]], full, c, shred_win(c));
                 if (avail < x0) {
                     const int so = si ^ 1;
                     if ((r = collect(so))) return r;
@@ -1295,13 +1152,12 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             uint64_t need = 0;
             size_t e = b;
             while (e < idx.size()) {
-                const uint64_t x = zmw_bytes(z[idx[e]], full, c, c->shred_caps ? c->shred_read_cap : 0u);
+                const uint64_t x = zmw_bytes(z[idx[e]], full, c, shred_win(c));
                 if (e > b && (need + x > lim || cls[idx[e]] != cls[idx[b]] || e == cut)) break;
                 need += x;
                 ++e;
             }
-            if (lim < slot_budget && (e < idx.size() && e != cut && need + zmw_bytes(z[idx[e]], full, c,
-                                                                                c->shred_caps ? c->shred_read_cap : 0u) <= slot_budget &&
+            if (lim < slot_budget && (e < idx.size() && e != cut && need + zmw_bytes(z[idx[e]], full, c, shred_win(c)) <= slot_budget &&
                                       cls[idx[e]] == cls[idx[b]]))
                 ++c->mem_replans;  // cut below the plan by the free memory
             sub.resize(e - b);
@@ -1350,21 +1206,10 @@ int ccsx_gpu_run(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, ccsx_zm
             if (s.inflight) (void)hipStreamSynchronize(s.stream), s.inflight = false;
         return r;
     }
-    if (c->fault >= 0 && (size_t)c->fault < nz) {
-        out[c->fault].status = ccsx::kErrTrace;
-        out[c->fault].len = 0;
-        if (c->quality) c->run_qlen[c->fault] = 0;
-        if (c->pass_stats) c->run_pst.ok[c->fault] = 0;
-        if (c->base_map) c->run_bm.ok[c->fault] = 0;
-        if (c->pileup) c->run_pu.ok[c->fault] = 0;
-        if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
-    }
+    inject_fault(c->fault, c->run, out, first_err);
     c->fault = -1;
-    for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(c->run_arena.data() + aoff[i]);
-    if (c->quality) c->last_qual = 1;
-    if (c->pass_stats) c->last_pst = 1;
-    if (c->base_map) c->last_bm = 1;
-    if (c->pileup) c->last_pu = 1;
+    for (size_t i = 0; i < nz; ++i) out[i].ccs = c->run.ccs(i);
+    c->last = 1;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1397,7 +1242,7 @@ int ccsx_gpu_reserve_staging(ccsx_ctx *c, uint64_t seq_bytes, uint64_t out_bytes
         if (c->tk[k].pending) continue;
         Slot &s = c->slot[k];
         HIPCHK(c, s.h_seq.reserve(seq_bytes, 0, true));
-        HIPCHK(c, s.h_out.reserve(out_bytes * (c->quality ? 2 : 1), 0, true));  // (the quality plane too)
+        HIPCHK(c, s.h_out.reserve(out_bytes * (c->side & ccsx::side_bit(ccsx::kSideQual) ? 2 : 1), 0, true));  // (the quality plane too)
         break;
     }
     return 0;
@@ -1430,7 +1275,7 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     uint64_t tot = 0;
     bool one_class = true;
     for (size_t i = 0; i < nz; ++i) {
-        tot += zmw_bytes(z[i], false, c, c->shred_caps ? c->shred_read_cap : 0u);
+        tot += zmw_bytes(z[i], false, c, shred_win(c));
         one_class = one_class && zmw_class(z[i], c->shred_caps) == zmw_class(z[0], c->shred_caps);
     }
     if (tot > slot_budget || !one_class) {
@@ -1441,10 +1286,7 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
         c->err = m;
         return -4;
     }
-    if (si == 0 && c->last_qual == 2) c->last_qual = 0;  // (slot 0's fetched results go with its arenas)
-    if (si == 0 && c->last_pst == 2) c->last_pst = 0;
-    if (si == 0 && c->last_bm == 2) c->last_bm = 0;
-    if (si == 0 && c->last_pu == 2) c->last_pu = 0;
+    if (si == 0 && c->last == 2) c->last = 0;  // (slot 0's fetched results go with its arenas)
     r = stage_slot(c, s, z, nz, 0, 0);
     if (!r) r = launch_slot(c, s, mode);
     c->shred_caps = false;
@@ -1455,14 +1297,8 @@ int ccsx_gpu_submit(ccsx_ctx *c, int mode, const ccsx_zmw_in *z, size_t nz, int 
     c->tk[si].z = z;
     c->tk[si].nz = nz;
     c->tk[si].fault = c->fault;
-    c->tk[si].qual = s.qual;
-    c->tk[si].has_qual = false;
-    c->tk[si].pstat = s.pstat;
-    c->tk[si].has_pst = false;
-    c->tk[si].bmap = s.bmap;
-    c->tk[si].has_bm = false;
-    c->tk[si].pile = s.pile;
-    c->tk[si].has_pu = false;
+    c->tk[si].side = s.lay.mask;
+    c->tk[si].collected = false;
     c->fault = -1;
     *slot = si;
     return 0;
@@ -1483,84 +1319,18 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
     std::vector<ccsx_zmw_out> o(nz);
     int r = fetch_slot(c, s, o.data());
     if (r && r != -2) return r;
-    std::vector<uint64_t> aoff(nz, 0);
     std::vector<uint32_t> retry;
     std::string first_err;
-    t.arena.clear();
-    t.has_qual = false;
-    t.qarena.clear();
-    t.qoff.assign(t.qual ? nz : 0, 0);
-    t.qlen.assign(t.qual ? nz : 0, 0);
+    t.res.reset(nz, t.side);
     // the full-cap re-run below stages as the batch was submitted, whatever
-    // ccsx_gpu_set_quality said since
-    struct Quality {
+    // the ccsx_gpu_set_* of the optional outputs said since
+    struct Side {
         ccsx_ctx *c;
-        bool was;
-        Quality(ccsx_ctx *x, bool on) : c(x), was(x->quality) { c->quality = on; }
-        ~Quality() { c->quality = was; }
-    } quality(c, t.qual);
-    t.has_pst = false;
-    t.pst.reset(t.pstat ? nz : 0);
-    struct PassStats {
-        ccsx_ctx *c;
-        bool was;
-        PassStats(ccsx_ctx *x, bool on) : c(x), was(x->pass_stats) { c->pass_stats = on; }
-        ~PassStats() { c->pass_stats = was; }
-    } pass_stats(c, t.pstat);
-    t.has_bm = false;
-    t.bm.reset(t.bmap ? nz : 0);
-    struct BaseMap {
-        ccsx_ctx *c;
-        bool was;
-        BaseMap(ccsx_ctx *x, bool on) : c(x), was(x->base_map) { c->base_map = on; }
-        ~BaseMap() { c->base_map = was; }
-    } base_map(c, t.bmap);
-    t.has_pu = false;
-    t.pu.reset(t.pile ? nz : 0);
-    struct Pileup {
-        ccsx_ctx *c;
-        bool was;
-        Pileup(ccsx_ctx *x, bool on) : c(x), was(x->pileup) { c->pileup = on; }
-        ~Pileup() { c->pileup = was; }
-    } pileup(c, t.pile);
-    auto gather = [&](const ccsx_zmw_out *res, const uint32_t *idx, size_t n, bool can_retry) {
-        size_t add = 0;
-        for (size_t i = 0; i < n; ++i) add += res[i].status ? 0 : res[i].len;
-        t.arena.reserve(t.arena.size() + add);
-        if (s.qual) t.qarena.reserve(t.qarena.size() + add);
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t g = idx ? idx[i] : (uint32_t)i;
-            out[g].cells = res[i].cells;
-            out[g].status = res[i].status;
-            out[g].len = 0;
-            if (res[i].status) {
-                if (can_retry && is_cap_error(res[i].status)) {
-                    retry.push_back(g);
-                } else if (first_err.empty()) {
-                    char m[200];
-                    snprintf(m, sizeof m, "ZMW %u of the batch failed on the device: %s", g,
-                             ccsx_gpu_status_str(res[i].status));
-                    first_err = m;
-                }
-                continue;
-            }
-            aoff[g] = t.arena.size();
-            out[g].len = res[i].len;
-            t.arena.insert(t.arena.end(), res[i].ccs, res[i].ccs + res[i].len);
-            if (s.qual) {
-                // (res[i].ccs points into the slot's CCS plane; the quality plane lies out_bytes behind)
-                const uint8_t *q = reinterpret_cast<const uint8_t *>(res[i].ccs) + s.out_bytes;
-                t.qoff[g] = t.qarena.size();
-                t.qlen[g] = res[i].len;
-                t.qarena.insert(t.qarena.end(), q, q + res[i].len);
-            }
-            // (gather's results are the slot's, in its order: ZMW i of the slot)
-            if (s.pstat) t.pst.put(g, s.h_pstat(i), s.desc[i].n);
-            if (s.bmap) t.bm.put(g, s.h_bmap(i), s.hlen.data() + s.desc[i].seg0, s.desc[i].n);
-            if (s.pile) t.pu.put(g, s.h_pile(i), res[i].len);
-        }
-    };
-    gather(o.data(), nullptr, nz, true);
+        ccsx::SideMask was;
+        Side(ccsx_ctx *x, ccsx::SideMask m) : c(x), was(x->side) { c->side = m; }
+        ~Side() { c->side = was; }
+    } side(c, t.side);
+    gather_slice(s, o.data(), nullptr, t.res, out, &retry, first_err);
     if (!retry.empty()) {
         // ZMWs that outgrew a tight cap: full caps, on this slot, slices of
         // at most the slot budget (rare: none of 500,000 config-E ZMWs)
@@ -1576,7 +1346,7 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
             uint64_t need = 0;
             size_t e = b;
             while (e < todo.size()) {
-                const uint64_t x = zmw_bytes(z[todo[e]], true, c, c->shred_caps ? c->shred_read_cap : 0u);
+                const uint64_t x = zmw_bytes(z[todo[e]], true, c, shred_win(c));
                 if (e > b && need + x > slot_budget) break;
                 need += x;
                 ++e;
@@ -1589,7 +1359,7 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
                 o.assign(sub.size(), ccsx_zmw_out{});
                 r = fetch_slot(c, s, o.data());
                 if (r == -2) r = 0;
-                if (!r) gather(o.data(), todo.data() + b, sub.size(), false);
+                if (!r) gather_slice(s, o.data(), todo.data() + b, t.res, out, nullptr, first_err);
             }
             ++c->slices;
             b = e;
@@ -1597,20 +1367,9 @@ int ccsx_gpu_collect(ccsx_ctx *c, int si, ccsx_zmw_out *out)
         c->shred_caps = false;
         if (r) return r;
     }
-    if (t.fault >= 0 && (size_t)t.fault < nz) {
-        out[t.fault].status = ccsx::kErrTrace;
-        out[t.fault].len = 0;
-        if (t.qual) t.qlen[t.fault] = 0;
-        if (t.pstat) t.pst.ok[t.fault] = 0;
-        if (t.bmap) t.bm.ok[t.fault] = 0;
-        if (t.pile) t.pu.ok[t.fault] = 0;
-        if (first_err.empty()) first_err = "ZMW failed on the device: injected fault (test hook)";
-    }
-    for (size_t i = 0; i < nz; ++i) out[i].ccs = reinterpret_cast<const char *>(t.arena.data() + aoff[i]);
-    t.has_qual = t.qual;
-    t.has_pst = t.pstat;
-    t.has_bm = t.bmap;
-    t.has_pu = t.pile;
+    inject_fault(t.fault, t.res, out, first_err);
+    for (size_t i = 0; i < nz; ++i) out[i].ccs = t.res.ccs(i);
+    t.collected = true;
     if (!first_err.empty()) {
         c->err = first_err;
         return -2;
@@ -1737,11 +1496,35 @@ int ccsx_gpu_bp_log(const ccsx_ctx *c, size_t zmw, const uint32_t **pairs, uint3
     return 0;
 }
 
-int ccsx_gpu_set_quality(ccsx_ctx *c, int on)
+static int set_side(ccsx_ctx *c, int o, int on)
 {
     if (!c) return -1;
-    c->quality = on != 0;
+    c->side = on ? c->side | ccsx::side_bit(o) : c->side & ~ccsx::side_bit(o);
     return 0;
+}
+
+int ccsx_gpu_set_quality(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideQual, on); }
+int ccsx_gpu_set_pass_stats(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSidePass, on); }
+int ccsx_gpu_set_base_map(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideMap, on); }
+int ccsx_gpu_set_pileup(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSidePile, on); }
+
+// The accessors' common part: output o of ZMW `zmw` of the batch collected from
+// `slot`, or (slot -1) of the last ccsx_gpu_run's gathered results or the slice
+// ccsx_gpu_fetch left in slot 0.  Returns 0 and r, or -1 with the refusal in
+// c->err (side_out.h side_find: off, beyond the batch, failed).
+static int side_lookup(ccsx_ctx *c, int slot, size_t zmw, int o, ccsx::SideRec &r)
+{
+    if (slot < -1 || slot > 1) {
+        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
+        return -1;
+    }
+    const char *e = ccsx::kSide[o].off;
+    if (slot >= 0 && c->tk[slot].pending) e = "that slot's batch is not collected yet";
+    else if (slot >= 0 && c->tk[slot].collected) e = ccsx::side_find(c->tk[slot].res, o, zmw, r);
+    else if (slot < 0 && c->last == 1) e = ccsx::side_find(c->run, o, zmw, r);
+    else if (slot < 0 && c->last == 2) e = ccsx::side_find(c->slot[0].view(), o, zmw, r);
+    if (e) c->err = e;
+    return e ? -1 : 0;
 }
 
 int ccsx_gpu_quality(ccsx_ctx *c, int slot, size_t zmw, const uint8_t **qual, uint32_t *len)
@@ -1749,115 +1532,22 @@ int ccsx_gpu_quality(ccsx_ctx *c, int slot, size_t zmw, const uint8_t **qual, ui
     if (!c || !qual || !len) return -1;
     *qual = nullptr;
     *len = 0;
-    if (slot < -1 || slot > 1) {
-        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
-        return -1;
-    }
-    const char *off = "that batch ran with quality off (ccsx_gpu_set_quality)";
-    const char *range = "ZMW index beyond the batch";
-    if (slot >= 0) {
-        const auto &t = c->tk[slot];
-        if (t.pending || !t.has_qual) {
-            c->err = t.pending ? "that slot's batch is not collected yet" : off;
-            return -1;
-        }
-        if (zmw >= t.qlen.size()) {
-            c->err = range;
-            return -1;
-        }
-        *qual = t.qarena.data() + t.qoff[zmw];
-        *len = t.qlen[zmw];
-        return 0;
-    }
-    if (c->last_qual == 1) {
-        if (zmw >= c->run_qlen.size()) {
-            c->err = range;
-            return -1;
-        }
-        *qual = c->run_qual.data() + c->run_qoff[zmw];
-        *len = c->run_qlen[zmw];
-        return 0;
-    }
-    const Slot &s = c->slot[0];
-    if (c->last_qual != 2 || !s.qual) {
-        c->err = off;
-        return -1;
-    }
-    if (zmw >= s.nz) {
-        c->err = range;
-        return -1;
-    }
-    *qual = s.h_out.p + s.out_bytes + s.desc[zmw].out_off;
-    *len = s.h_status[zmw] ? 0 : s.h_olen[zmw];
-    return 0;
-}
-
-int ccsx_gpu_set_pass_stats(ccsx_ctx *c, int on)
-{
-    if (!c) return -1;
-    c->pass_stats = on != 0;
+    ccsx::SideRec r;
+    if (side_lookup(c, slot, zmw, ccsx::kSideQual, r)) return -1;
+    *qual = r.qual;
+    *len = r.len;  // (0 for a ZMW without a CCS)
     return 0;
 }
 
 int ccsx_gpu_pass_stats(ccsx_ctx *c, int slot, size_t zmw, const ccsx_pass_stat **st, uint32_t *nseg)
 {
-    static_assert(sizeof(ccsx_pass_stat) == ccsx::kPassWords * 4, "ccsx_pass_stat is the kernel's record");
     if (!c || !st || !nseg) return -1;
     *st = nullptr;
     *nseg = 0;
-    if (slot < -1 || slot > 1) {
-        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
-        return -1;
-    }
-    const char *off = "that batch ran with pass statistics off (ccsx_gpu_set_pass_stats)";
-    const char *range = "ZMW index beyond the batch";
-    const char *failed = "that ZMW failed: it has no pass statistics";
-    const PassSet *ps = nullptr;
-    if (slot >= 0) {
-        const auto &t = c->tk[slot];
-        if (t.pending || !t.has_pst) {
-            c->err = t.pending ? "that slot's batch is not collected yet" : off;
-            return -1;
-        }
-        ps = &t.pst;
-    } else if (c->last_pst == 1) {
-        ps = &c->run_pst;
-    }
-    if (ps) {
-        if (zmw >= ps->nseg.size()) {
-            c->err = range;
-            return -1;
-        }
-        if (!ps->ok[zmw]) {
-            c->err = failed;
-            return -1;
-        }
-        *st = reinterpret_cast<const ccsx_pass_stat *>(ps->words.data() + ps->off[zmw]);
-        *nseg = ps->nseg[zmw];
-        return 0;
-    }
-    const Slot &s = c->slot[0];
-    if (c->last_pst != 2 || !s.pstat) {
-        c->err = off;
-        return -1;
-    }
-    if (zmw >= s.nz) {
-        c->err = range;
-        return -1;
-    }
-    if (s.h_status[zmw]) {
-        c->err = failed;
-        return -1;
-    }
-    *st = reinterpret_cast<const ccsx_pass_stat *>(s.h_pstat(zmw));
-    *nseg = s.desc[zmw].n;
-    return 0;
-}
-
-int ccsx_gpu_set_base_map(ccsx_ctx *c, int on)
-{
-    if (!c) return -1;
-    c->base_map = on != 0;
+    ccsx::SideRec r;
+    if (side_lookup(c, slot, zmw, ccsx::kSidePass, r)) return -1;
+    *st = reinterpret_cast<const ccsx_pass_stat *>(r.pass);
+    *nseg = r.nseg;
     return 0;
 }
 
@@ -1866,71 +1556,14 @@ int ccsx_gpu_base_map(ccsx_ctx *c, int slot, size_t zmw, uint32_t seg, const uin
     if (!c || !map || !len) return -1;
     *map = nullptr;
     *len = 0;
-    if (slot < -1 || slot > 1) {
-        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
+    ccsx::SideRec r;
+    if (side_lookup(c, slot, zmw, ccsx::kSideMap, r)) return -1;
+    if (seg >= r.nseg) {
+        c->err = "segment index beyond the ZMW's segments";
         return -1;
     }
-    const char *off = "that batch ran with the base map off (ccsx_gpu_set_base_map)";
-    const char *range = "ZMW index beyond the batch";
-    const char *srange = "segment index beyond the ZMW's segments";
-    const char *failed = "that ZMW failed: it has no base map";
-    const MapSet *ms = nullptr;
-    if (slot >= 0) {
-        const auto &t = c->tk[slot];
-        if (t.pending || !t.has_bm) {
-            c->err = t.pending ? "that slot's batch is not collected yet" : off;
-            return -1;
-        }
-        ms = &t.bm;
-    } else if (c->last_bm == 1) {
-        ms = &c->run_bm;
-    }
-    if (ms) {
-        if (zmw >= ms->nseg.size()) {
-            c->err = range;
-            return -1;
-        }
-        if (!ms->ok[zmw]) {
-            c->err = failed;
-            return -1;
-        }
-        if (seg >= ms->nseg[zmw]) {
-            c->err = srange;
-            return -1;
-        }
-        *map = ms->words.data() + ms->spos[ms->seg0[zmw] + seg];
-        *len = ms->slen[ms->seg0[zmw] + seg];
-        return 0;
-    }
-    const Slot &s = c->slot[0];
-    if (c->last_bm != 2 || !s.bmap) {
-        c->err = off;
-        return -1;
-    }
-    if (zmw >= s.nz) {
-        c->err = range;
-        return -1;
-    }
-    if (s.h_status[zmw]) {
-        c->err = failed;
-        return -1;
-    }
-    if (seg >= s.desc[zmw].n) {
-        c->err = srange;
-        return -1;
-    }
-    const uint32_t *ln = s.hlen.data() + s.desc[zmw].seg0;
-    uint64_t at = 0;
-    for (uint32_t k = 0; k < seg; ++k) at += ln[k];
-    *map = s.h_bmap(zmw) + at;
-    *len = ln[seg];
-    return 0;
-}
-
-int ccsx_gpu_set_pileup(ccsx_ctx *c, int on)
-{
-    if (!c) return -1;
-    c->pileup = on != 0;
+    *map = r.map_seg(seg);
+    *len = r.seg_len[seg];
     return 0;
 }
 
@@ -1939,55 +1572,12 @@ int ccsx_gpu_pileup(ccsx_ctx *c, int slot, size_t zmw, const ccsx_pileup **p, ui
     if (!c || !p || !len) return -1;
     *p = nullptr;
     *len = 0;
-    if (slot < -1 || slot > 1) {
-        c->err = "slot must be -1 (the last run / fetch) or a collected submit slot";
-        return -1;
-    }
-    const char *off = "that batch ran with the pileup off (ccsx_gpu_set_pileup)";
-    const char *range = "ZMW index beyond the batch";
-    const char *failed = "that ZMW failed: it has no pileup";
-    const PileSet *ps = nullptr;
-    if (slot >= 0) {
-        const auto &t = c->tk[slot];
-        if (t.pending || !t.has_pu) {
-            c->err = t.pending ? "that slot's batch is not collected yet" : off;
-            return -1;
-        }
-        ps = &t.pu;
-    } else if (c->last_pu == 1) {
-        ps = &c->run_pu;
-    }
-    if (ps) {
-        if (zmw >= ps->len.size()) {
-            c->err = range;
-            return -1;
-        }
-        if (!ps->ok[zmw]) {
-            c->err = failed;
-            return -1;
-        }
-        *p = ps->recs.data() + ps->off[zmw];
-        *len = ps->len[zmw];
-        return 0;
-    }
-    const Slot &s = c->slot[0];
-    if (c->last_pu != 2 || !s.pile) {
-        c->err = off;
-        return -1;
-    }
-    if (zmw >= s.nz) {
-        c->err = range;
-        return -1;
-    }
-    if (s.h_status[zmw]) {
-        c->err = failed;
-        return -1;
-    }
-    *p = s.h_pile(zmw);
-    *len = s.h_olen[zmw];
+    ccsx::SideRec r;
+    if (side_lookup(c, slot, zmw, ccsx::kSidePile, r)) return -1;
+    *p = r.pile;
+    *len = r.len;
     return 0;
 }
-
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -2038,7 +1628,7 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + (s.qual ? s.out_bytes : 0) + s.pst_bytes() + s.bm_bytes() + s.pu_bytes() + s.srev_bytes() +
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + ccsx::side_bytes_of(s.lay.mask, s.out_bytes, s.nseg_total, s.nbase_total) +
            s.msa_bytes;
 }
 

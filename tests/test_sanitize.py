@@ -22,7 +22,8 @@ SRCS = ["tools/host_sanitize.cpp"] + [f"ccsx_amd/csrc/host/{f}.cpp" for f in
 def sanitized():
     os.makedirs(os.path.dirname(EXE), exist_ok=True)
     srcs = [os.path.join(ROOT, s) for s in SRCS]
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in srcs):
+    deps = srcs + [os.path.join(ROOT, "ccsx_amd", "csrc", "side_out.h")]
+    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in deps):
         subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"), "-I",
                         os.path.join(ROOT, "ccsx_amd", "csrc", "host"), "-o", EXE] + srcs + ["-lz", "-lpthread"],

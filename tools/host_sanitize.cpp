@@ -1,6 +1,6 @@
 // host_sanitize.cpp -- drives the host C++ of the product (ingest, seqio C-ABI,
 // ccs_prepare, the pairwise aligner, the synthetic source, the dispatch
-// partitioner) under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.
+// partitioner, the engine's optional-output bookkeeping of side_out.h) under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.
 // tests/test_sanitize.py compiles it together with those sources
 // (-fsanitize=address,undefined; no HIP code is involved) and runs it on the
 // golden ingest fixtures and synthetic ZMWs.
@@ -16,8 +16,140 @@
 
 #include "ccsx_host.h"
 #include "ccsx_seqio.h"
+#include "../ccsx_amd/csrc/side_out.h"  // (by path: it and ccsx_layout.h beside it are not on the include path of this build)
 
 static uint32_t crc(const char *p, size_t n) { return (uint32_t)crc32(0, reinterpret_cast<const unsigned char *>(p), (uInt)n); }
+
+// side_out.h on synthetic slices of 0, 1 and 5 ZMWs under all 16 masks: a ZMW
+// without a segment, one with an odd output slab (the slice's slabs then end off
+// a multiple of 8), one with an empty segment, one failed.  Returns 0 or the
+// number of the check that failed.
+static int side_outputs()
+{
+    using namespace ccsx;
+    struct Z {
+        std::vector<uint32_t> lens;
+        uint32_t outcap, status;
+    };
+    const std::vector<Z> five = {{{7, 5, 9}, 40, 0}, {{}, 16, 0}, {{4, 0}, 33, 0}, {{11}, 24, kErrOut}, {{3, 3, 3, 2}, 32, 0}};
+    const std::vector<Z> one = {five[2]};
+    const size_t perm5[5] = {2, 4, 0, 3, 1};
+    const size_t align[kSideCount] = {1, alignof(uint32_t), alignof(uint32_t), alignof(ccsx_pileup)};
+    for (SideMask m = 0; m <= kSideAll; ++m)
+        for (const std::vector<Z> *zs : {(const std::vector<Z> *)nullptr, &one, &five}) {
+            const size_t nz = zs ? zs->size() : 0;
+            // the slice's tables, as stage_slot lays them out
+            std::vector<ZmwDesc> desc(nz);
+            std::vector<uint32_t> seg_len, out_len(nz);
+            std::vector<uint64_t> map_off(nz);
+            std::vector<int32_t> status(nz);
+            uint64_t slab = 0, nbase = 0, per_zmw[kSideCount] = {};
+            for (size_t i = 0; i < nz; ++i) {
+                const Z &z = (*zs)[i];
+                uint64_t S = 0;
+                for (uint32_t l : z.lens) S += l;
+                desc[i].seg0 = (uint32_t)seg_len.size();
+                desc[i].n = (uint32_t)z.lens.size();
+                desc[i].out_off = slab;
+                desc[i].outcap = z.outcap;
+                map_off[i] = nbase;
+                status[i] = (int32_t)z.status;
+                out_len[i] = z.outcap - 3;
+                for (int o = 0; o < kSideCount; ++o) per_zmw[o] += side_bytes(o, z.outcap, z.lens.size(), S);
+                seg_len.insert(seg_len.end(), z.lens.begin(), z.lens.end());
+                slab += z.outcap, nbase += S;
+            }
+            if (nz && slab % 8 == 0) return 50;
+            // sizes: a slice's is the sum of its ZMWs', per output and for the mask
+            uint64_t sum = 0;
+            for (int o = 0; o < kSideCount; ++o) {
+                if (side_bytes(o, slab, seg_len.size(), nbase) != per_zmw[o]) return 51;
+                if (m & side_bit(o)) sum += per_zmw[o];
+            }
+            if (side_bytes_of(m, slab, seg_len.size(), nbase) != sum) return 52;
+            // layout: the planes in order, none overlapping, each aligned for its
+            // elements, less than 8 bytes of padding before each; the total is
+            // the CCS plane, the enabled outputs and that padding
+            SideLayout L;
+            L.plan(m, slab, seg_len.size(), nbase);
+            uint64_t end = slab, pad = 0;
+            for (int o = 0; o < kSideCount; ++o) {
+                if (!(m & side_bit(o))) {
+                    if (L.has(o) || L.bytes[o] || L.plane[o]) return 53;
+                    continue;
+                }
+                if (!L.has(o) || L.off[o] < end || L.off[o] - end >= 8 || L.off[o] % align[o]) return 54;
+                if (L.bytes[o] != side_bytes(o, slab, seg_len.size(), nbase) || L.plane[o] > L.bytes[o]) return 55;
+                if (kSide[o].in_out && (L.off[o] != end || L.out_dev != L.off[o] + L.plane[o])) return 56;
+                pad += L.off[o] - end;
+                end = L.off[o] + L.bytes[o];
+            }
+            if (L.total != end || L.total != slab + sum + pad || L.out_dev < slab) return 57;
+            // fake planes: every byte derived from its index (exactly L.total
+            // bytes, so a read past a plane's end is one past the allocation)
+            std::vector<uint8_t> h(L.total);
+            for (size_t j = 0; j < h.size(); ++j) h[j] = uint8_t(j * 131 + m * 7 + 1);
+            const SideView v{&L, h.data(), nz, desc.data(), seg_len.data(), map_off.data(), status.data(), out_len.data()};
+            // gathered in a permuted input order: ZMW i of the slice is input perm[i]
+            Gathered G;
+            G.reset(nz, m);
+            size_t add = 0;
+            for (size_t i = 0; i < nz; ++i) add += status[i] ? 0 : out_len[i];
+            G.grow(add);
+            std::vector<size_t> perm(nz, 0), slice_of(nz, 0);
+            for (size_t i = 0; i < nz; ++i) perm[i] = nz == 5 ? perm5[i] : i, slice_of[perm[i]] = i;
+            for (size_t i = 0; i < nz; ++i)
+                if (!status[i]) G.put(perm[i], v.rec(i));
+            // every ZMW back through the lookup, from the gathered batch and from the slice itself
+            for (int o = 0; o < kSideCount; ++o)
+                for (size_t g = 0; g <= nz; ++g) {
+                    SideRec r[2];
+                    const char *e[2] = {side_find(G, o, g, r[0]), g < nz ? side_find(v, o, slice_of[g], r[1]) : side_find(v, o, g, r[1])};
+                    for (int k = 0; k < 2; ++k) {
+                        if (!(m & side_bit(o))) {
+                            if (e[k] != kSide[o].off) return 58;
+                            continue;
+                        }
+                        if (g == nz) {
+                            if (!e[k] || std::string(e[k]) != "ZMW index beyond the batch") return 59;
+                            continue;
+                        }
+                        const size_t i = slice_of[g];
+                        const ZmwDesc &d = desc[i];
+                        if (status[i]) {
+                            if (e[k] != kSide[o].failed || r[k].ok || r[k].len) return 60;
+                            continue;
+                        }
+                        if (e[k] || !r[k].ok || r[k].len != out_len[i] || r[k].nseg != d.n) return 61;
+                        if (memcmp(r[k].ccs, h.data() + d.out_off, r[k].len)) return 62;
+                        if (o == kSideQual && memcmp(r[k].qual, h.data() + L.off[o] + d.out_off, r[k].len)) return 63;
+                        if (o == kSidePass &&
+                            memcmp(r[k].pass, h.data() + L.off[o] + size_t(d.seg0) * kPassWords * 4, size_t(d.n) * kPassWords * 4))
+                            return 64;
+                        if (o == kSidePile && memcmp(r[k].pile, h.data() + L.off[o] + d.out_off * kPuBytes, size_t(r[k].len) * kPuBytes))
+                            return 65;
+                        if (o == kSideMap) {
+                            uint64_t at = map_off[i];
+                            for (uint32_t s = 0; s < d.n; ++s) {
+                                if (r[k].seg_len[s] != seg_len[d.seg0 + s]) return 66;
+                                if (memcmp(r[k].map_seg(s), h.data() + L.off[o] + at * 4, size_t(seg_len[d.seg0 + s]) * 4)) return 67;
+                                at += seg_len[d.seg0 + s];
+                            }
+                        }
+                    }
+                }
+            // the injected fault: a gathered ZMW dropped afterwards has no result in any output
+            if (nz) {
+                G.drop(perm[0]);
+                for (int o = 0; o < kSideCount; ++o) {
+                    SideRec r;
+                    if ((m & side_bit(o)) && (side_find(G, o, perm[0], r) != kSide[o].failed || r.ok || r.len)) return 68;
+                }
+            }
+        }
+    printf("side outputs %d masks\n", (int)kSideAll + 1);
+    return 0;
+}
 
 int main(int argc, char **argv)
 {
@@ -104,6 +236,9 @@ int main(int argc, char **argv)
                                            order.data(), bounds.data());
         if (nb > n || bounds[nb] != n) return 7;
     }
+    // 5. the engine's optional outputs (side_out.h): sizes, slice layout,
+    // gathering and lookup, for every subset of the outputs
+    if (const int r = side_outputs()) return r;
     printf("ok\n");
     return 0;
 }
