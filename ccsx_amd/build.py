@@ -125,6 +125,7 @@ def build_product(verbose: bool = False) -> str:
         os.path.join(CSRC, "host", "passstat.cpp"),
         os.path.join(CSRC, "host", "basemap.cpp"),
         os.path.join(CSRC, "host", "pileup.cpp"),
+        os.path.join(CSRC, "host", "kinetics.cpp"),
     ]
     common = ["-O3", "-std=c++17", "-fPIC", "-I" + INC, "-I" + CSRC, "-I" + os.path.join(CSRC, "host")]
     # the kernel's per-ZMW chains are latency-bound: the ILP-maximising machine

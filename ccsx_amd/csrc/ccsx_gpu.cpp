@@ -5,7 +5,7 @@
 // launches one workgroup per ZMW and copies the CCS strings back; slices of
 // a large chunk alternate between two slots (streams) so they overlap.
 // The optional per-ZMW outputs beside the CCS (qualities, pass records, map,
-// pileup) are described once, in side_out.h: their sizes, their planes in a
+// pileup, kinetics) are described once, in side_out.h: their sizes, their planes in a
 // fetched slice, the container a batch's results are gathered into and the
 // accessors' lookup; here they are a mask, loops over it, and their wiring
 // into the kernel's arguments (launch_slot).
@@ -199,11 +199,15 @@ struct Slot {
     // ZMW lie within the 32 that every size counts for a ZMW's tables);
     // kPuBytes per byte of the output slab in d_side[kSidePile], the record of
     // a base at its slab offset, and a strand flag per segment in d_srev
-    // (hsrev: the host copy, the index space of hlen)
+    // (hsrev: the host copy, the index space of hlen); kKnBytes per byte of
+    // the output slab in d_side[kSideKin], its input -- the ipd plane and
+    // behind it the pw plane, a byte per pushed base each in the map's index
+    // space (hbmoff) -- in d_kin_in (packed in h_kin) and a kinetics strand
+    // byte per segment in d_ksrev (hksrev)
     ccsx::SideLayout lay;
     uint64_t nbase_total = 0;          // pushed bases of the slice
     std::vector<uint64_t> hbmoff;
-    std::vector<uint8_t> hsrev;
+    std::vector<uint8_t> hsrev, hksrev;
     // the fetched slice as the gathering and the accessors read it
     ccsx::SideView view() const
     {
@@ -214,8 +218,8 @@ struct Slot {
     DevBuf d_prof, d_bp;
     DevBuf d_seq, d_soff, d_slen, d_desc, d_order, d_ws, d_out, d_msa, d_olen, d_ncols, d_status, d_cells;
     DevBuf d_side[ccsx::kSideCount];   // the planes with a buffer of their own (not SideInfo::in_out)
-    DevBuf d_bmoff, d_srev;
-    HostBuf h_out, h_seq;
+    DevBuf d_bmoff, d_srev, d_ksrev, d_kin_in;
+    HostBuf h_out, h_seq, h_kin;
     std::vector<uint32_t> h_olen, h_ncols, h_bp;
     std::vector<int32_t> h_status;
     std::vector<unsigned long long> h_cells, h_prof;
@@ -223,7 +227,7 @@ struct Slot {
     void release()
     {
         DevBuf *bufs[] = {&d_bp, &d_prof, &d_seq, &d_soff, &d_slen, &d_desc, &d_order, &d_ws, &d_out,
-                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_bmoff, &d_srev};
+                          &d_msa, &d_olen, &d_ncols, &d_status, &d_cells, &d_bmoff, &d_srev, &d_ksrev, &d_kin_in};
         for (DevBuf *b : bufs) b->release();
         for (DevBuf &b : d_side) b.release();
         if (ev0) (void)hipEventDestroy(ev0);
@@ -355,7 +359,7 @@ void ccsx_gpu_close(ccsx_ctx *c)
         s.release();
     }
     const auto t1 = std::chrono::steady_clock::now();
-    for (Slot &s : c->slot) s.h_out.release(), s.h_seq.release();
+    for (Slot &s : c->slot) s.h_out.release(), s.h_seq.release(), s.h_kin.release();
     const auto t2 = std::chrono::steady_clock::now();
     delete c;
     if (getenv("CCSX_TIMING") && atoi(getenv("CCSX_TIMING")))
@@ -444,7 +448,7 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::zcaps(d, S, lmax, zi.nseg, full, c->tight_rows, shred_win, c->tight_out, c->tight_far);
     ccsx::ZLayout L;
     ccsx::zlayout(L, d);
-    return ccsx::align256(L.total) + hi + d.outcap + ccsx::side_bytes_of(c->side, d.outcap, zi.nseg, S) +
+    return ccsx::align256(L.total) + hi + d.outcap + ccsx::side_need_of(c->side, d.outcap, zi.nseg, S) +
            uint64_t(zi.nseg) * 8 + sizeof(ccsx::ZmwDesc) + 32;
 }
 
@@ -460,6 +464,7 @@ static int slot_avail(ccsx_ctx *c, const Slot &s, uint64_t &avail)
     HIPCHK(c, hipMemGetInfo(&freeb, &totb));
     uint64_t have = freeb + s.d_ws.cap + s.d_seq.cap + s.d_out.cap + s.d_msa.cap;
     for (const DevBuf &b : s.d_side) have += b.cap;
+    have += s.d_kin_in.cap;
     avail = have > (1ull << 30) ? have - (1ull << 30) : 0;
     return 0;
 }
@@ -502,7 +507,9 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     uint32_t nseg = 0, lmax_all = 0, nmax = 0;
     const ccsx::SideMask side = with_msa ? 0 : c->side;
     const bool with_map = (side & ccsx::side_bit(ccsx::kSideMap)) != 0;
-    s.hbmoff.resize(with_map ? nz : 0);
+    const bool with_kin = (side & ccsx::side_bit(ccsx::kSideKin)) != 0;
+    const bool with_bmoff = with_map || with_kin;  // the index space of the map and of the kinetics planes
+    s.hbmoff.resize(with_bmoff ? nz : 0);
     for (size_t i = 0; i < nz; ++i) {
         const ccsx_zmw_in &zi = z[i];
         uint64_t S, hi;
@@ -532,7 +539,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         d.bpcap = c->bp_log ? (full_caps ? uint32_t(S + 2) : uint32_t(S / 512 + 64)) : 0u;
         d.bp_off = bp_w;
         bp_w += c->bp_log ? 1 + 2 * uint64_t(d.bpcap) : 0;
-        if (with_map) s.hbmoff[i] = nbase;
+        if (with_bmoff) s.hbmoff[i] = nbase;
         nbase += S;
         nseg += zi.nseg;
         lmax_all = std::max(lmax_all, lmax);
@@ -598,7 +605,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + ccsx::side_bytes_of(side, out_b, nseg, nbase) + msa_b + bp_w * 4 +
+    const uint64_t need = seq_b + ws_b + out_b + ccsx::side_need_of(side, out_b, nseg, nbase) + msa_b + bp_w * 4 +
                           uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
@@ -628,7 +635,11 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, s.d_out.reserve(s.lay.out_dev));
     for (int o = 0; o < ccsx::kSideCount; ++o)
         if (!ccsx::kSide[o].in_out) HIPCHK(c, s.d_side[o].reserve(s.lay.plane[o]));
-    if (with_map) HIPCHK(c, s.d_bmoff.reserve(nz * 8));
+    if (with_bmoff) HIPCHK(c, s.d_bmoff.reserve(nz * 8));
+    if (with_kin) {
+        HIPCHK(c, s.d_ksrev.reserve(std::max<size_t>(nseg, 1)));
+        HIPCHK(c, s.d_kin_in.reserve(std::max<uint64_t>(2 * nbase, 1)));
+    }
     if (s.lay.has(ccsx::kSidePile)) HIPCHK(c, s.d_srev.reserve(nseg));
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
@@ -716,7 +727,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, hipMemcpyAsync(s.d_soff.p, s.hoff.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_slen.p, s.hlen.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_desc.p, s.desc.data(), nz * sizeof(ccsx::ZmwDesc), hipMemcpyHostToDevice, s.stream));
-    if (with_map && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
+    if (with_bmoff && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
     if (s.lay.has(ccsx::kSidePile)) {
         // the strand flags, read only here: a ZMW without them is all forward
         s.hsrev.assign(nseg, 0);
@@ -724,6 +735,30 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
             if (z[i].seg_rev)
                 for (uint32_t k = 0; k < z[i].nseg; ++k) s.hsrev[s.desc[i].seg0 + k] = z[i].seg_rev[k] ? 1 : 0;
         if (nseg) HIPCHK(c, hipMemcpyAsync(s.d_srev.p, s.hsrev.data(), nseg, hipMemcpyHostToDevice, s.stream));
+    }
+    if (with_kin) {
+        // the strand bytes and the two code planes, segment by segment in push
+        // order at the ZMW's place in the map's index space; a ZMW without
+        // planes stages zeros and kKnNone (its records are all zero)
+        s.hksrev.assign(nseg, 0);
+        HIPCHK(c, s.h_kin.reserve(2 * nbase));
+        uint8_t *hi = s.h_kin.p, *hp = s.h_kin.p + nbase;
+        for (size_t i = 0; i < nz; ++i) {
+            const ccsx_zmw_in &zi = z[i];
+            const bool have = zi.ipd && zi.pw;
+            uint64_t at = s.hbmoff[i];
+            for (uint32_t k = 0; k < zi.nseg; ++k) {
+                s.hksrev[s.desc[i].seg0 + k] =
+                    uint8_t((zi.seg_rev && zi.seg_rev[k] ? ccsx::kKnRev : 0) | (have ? 0 : ccsx::kKnNone));
+                const uint32_t ln = zi.seg_len[k];
+                if (!ln) continue;
+                if (have) memcpy(hi + at, zi.ipd + zi.seg_off[k], ln), memcpy(hp + at, zi.pw + zi.seg_off[k], ln);
+                else memset(hi + at, 0, ln), memset(hp + at, 0, ln);
+                at += ln;
+            }
+        }
+        if (nseg) HIPCHK(c, hipMemcpyAsync(s.d_ksrev.p, s.hksrev.data(), nseg, hipMemcpyHostToDevice, s.stream));
+        if (nbase) HIPCHK(c, hipMemcpyAsync(s.d_kin_in.p, s.h_kin.p, 2 * nbase, hipMemcpyHostToDevice, s.stream));
     }
     // launch order: decreasing estimated POA work (ccsx_zmw_cost: S x (28 +
     // n)), ties in input order -- longest-processing-time first, so a launch
@@ -771,9 +806,15 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     a.qual = L.has(ccsx::kSideQual) ? s.d_out.as<uint8_t>() + L.off[ccsx::kSideQual] : nullptr;
     a.pstat = L.plane[ccsx::kSidePass] ? s.d_side[ccsx::kSidePass].as<uint32_t>() : nullptr;
     a.bmap = L.plane[ccsx::kSideMap] ? s.d_side[ccsx::kSideMap].as<uint32_t>() : nullptr;
-    a.bmoff = L.plane[ccsx::kSideMap] ? s.d_bmoff.as<uint64_t>() : nullptr;
+    a.bmoff = L.plane[ccsx::kSideMap] || L.plane[ccsx::kSideKin] ? s.d_bmoff.as<uint64_t>() : nullptr;
     a.pile = L.plane[ccsx::kSidePile] ? s.d_side[ccsx::kSidePile].as<uint8_t>() : nullptr;
     a.srev = L.plane[ccsx::kSidePile] && s.nseg_total ? s.d_srev.as<uint8_t>() : nullptr;
+    if (L.plane[ccsx::kSideKin]) {
+        a.kin = s.d_side[ccsx::kSideKin].as<uint8_t>();
+        a.kipd = s.d_kin_in.as<uint8_t>();
+        a.kpw = s.d_kin_in.as<uint8_t>() + s.nbase_total;
+        a.ksrev = s.d_ksrev.as<uint8_t>();
+    }
     if (c->profiling) {
         HIPCHK(c, s.d_prof.reserve(s.nz * ccsx::kProfSlots * 8));
         a.prof = s.d_prof.as<unsigned long long>();
@@ -812,10 +853,10 @@ static int fetch_slot(ccsx_ctx *c, Slot &s, ccsx_zmw_out *out)
         for (int o = 0; o < ccsx::kSideCount; ++o) {
             if (ccsx::kSide[o].in_out || !L.plane[o]) continue;
             HIPCHK(c, hipMemcpyAsync(s.h_out.p + L.off[o], s.d_side[o].p, L.plane[o], hipMemcpyDeviceToHost, s.stream));
-            // (its flags, the pileup's strand flags, behind it)
+            // (its flags -- the pileup's strand flags, the kinetics' strand bytes -- behind it)
             if (L.bytes[o] > L.plane[o])
-                HIPCHK(c, hipMemcpyAsync(s.h_out.p + L.off[o] + L.plane[o], s.d_srev.p, L.bytes[o] - L.plane[o],
-                                         hipMemcpyDeviceToHost, s.stream));
+                HIPCHK(c, hipMemcpyAsync(s.h_out.p + L.off[o] + L.plane[o], (o == ccsx::kSideKin ? s.d_ksrev : s.d_srev).p,
+                                         L.bytes[o] - L.plane[o], hipMemcpyDeviceToHost, s.stream));
         }
         if (s.bp_words)
             HIPCHK(c, hipMemcpyAsync(s.h_bp.data(), s.d_bp.p, s.bp_words * 4, hipMemcpyDeviceToHost, s.stream));
@@ -1507,6 +1548,7 @@ int ccsx_gpu_set_quality(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideQu
 int ccsx_gpu_set_pass_stats(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSidePass, on); }
 int ccsx_gpu_set_base_map(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideMap, on); }
 int ccsx_gpu_set_pileup(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSidePile, on); }
+int ccsx_gpu_set_kinetics(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideKin, on); }
 
 // The accessors' common part: output o of ZMW `zmw` of the batch collected from
 // `slot`, or (slot -1) of the last ccsx_gpu_run's gathered results or the slice
@@ -1578,6 +1620,19 @@ int ccsx_gpu_pileup(ccsx_ctx *c, int slot, size_t zmw, const ccsx_pileup **p, ui
     *len = r.len;
     return 0;
 }
+
+int ccsx_gpu_kinetics(ccsx_ctx *c, int slot, size_t zmw, const ccsx_kinetics **rec, uint32_t *len)
+{
+    if (!c || !rec || !len) return -1;
+    *rec = nullptr;
+    *len = 0;
+    ccsx::SideRec r;
+    if (side_lookup(c, slot, zmw, ccsx::kSideKin, r)) return -1;
+    *rec = r.kin;
+    *len = r.len;
+    return 0;
+}
+
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -1628,7 +1683,7 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + ccsx::side_bytes_of(s.lay.mask, s.out_bytes, s.nseg_total, s.nbase_total) +
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + ccsx::side_need_of(s.lay.mask, s.out_bytes, s.nseg_total, s.nbase_total) +
            s.msa_bytes;
 }
 

@@ -3234,6 +3234,99 @@ __device__ __forceinline__ void base_map(const Z &z, uint32_t i, uint32_t n, uin
     }
 }
 
+// SPEC.md §13: the kinetics records of the CCS bases in the emitted columns
+// [0, i) of this POA call, into the ZMW's records kin (KArgs::kin at the ZMW's
+// output slab), from the per-base planes ipd / pw (KArgs::kipd / kpw at
+// KArgs::bmoff[zmw]: the map's index space) and the strand bytes ks (one per
+// read of the ZMW).  base_map's walk: per 64 reads (mask word w, lane = read,
+// carrying the entry of its read's next base) over the columns 64 at a time
+// (lane = column); per read bit the lanes whose column holds a base of the read
+// that matches the consensus (cmask) load that base's two codes -- consecutive
+// bytes across the lanes -- and add their frames to the sums of the read's
+// strand, which is wave-uniform (one ballot over ks per mask word).  After a
+// chunk's last mask word the base lanes divide, encode and store their record.
+// With more than 64 reads a column's sums cross the mask words through kKnPart
+// words per column in the DP's cell-record region (ZLayout::codes: dead between
+// the last traceback of a POA call and the next call's first DP row, rcap rows
+// of kRecRow >= kKnPart * 4 bytes for at most R <= rcap columns): word 0 stores
+// them, the words between add to them and the last one only reads them, so
+// nothing is zeroed and a second launch leaves the same plane.
+__device__ __forceinline__ void kinetics(const Z &z, uint32_t i, uint32_t n, uint32_t ol, const uint32_t *slen,
+                                         const uint32_t *pos0, const uint8_t *ks, const uint8_t *ipd, const uint8_t *pw,
+                                         uint8_t *kin)
+{
+    const uint32_t lane = lane_id(), nw = z.d.nw;
+    const uint64_t *mem = G_mem(z, z.cur);
+    if (i == 0) return;
+    uint32_t *part = P<uint32_t>(z, z.L.codes);
+    // (a ZMW staged without planes: every strand byte carries kKnNone)
+    const bool have = (uni((uint32_t)ks[0]) & kKnNone) == 0;
+    uint32_t seg = 0;  // entries of the segments before mask word w's
+    for (uint32_t w = 0; w * 64 < n; ++w) {
+        const uint32_t k = w * 64 + lane;
+        const uint32_t kn = n - w * 64 < 64 ? n - w * 64 : 64;
+        const bool lastw = (w + 1) * 64 >= n;
+        const uint32_t ln = k < n ? slen[k] : 0u;
+        const uint32_t end = seg + wave_incl_add(ln);  // one past read k's entries
+        uint32_t cur = end - ln + (pos0 && k < n ? pos0[k] : 0u);
+        seg = (uint32_t)__builtin_amdgcn_readlane((int)end, 63);
+        const uint64_t rw = ballot(k < n && (ks[k] & kKnRev) != 0);
+        uint32_t base = 0;  // base columns before c0
+        PsCols x0 = ps_cols(z, lane, i, w), x1 = ps_cols(z, 64 + lane, i, w);
+        uint64_t h = ps_rows(mem, x0.ra, x0.re, nw, w);
+        for (uint32_t c0 = 0; c0 < i; c0 += 64) {
+            const PsCols x2 = ps_cols(z, c0 + 128 + lane, i, w);
+            const uint64_t h1 = ps_rows(mem, x1.ra, x1.re, nw, w);
+            const uint64_t bb = ballot(x0.cb < 4);
+            const uint32_t t = ol + base + lanes_below(bb);
+            uint32_t *pp = part + (size_t)(c0 + lane) * kKnPart;
+            uint32_t s[2][3] = {{0, 0, 0}, {0, 0, 0}};  // per strand: ipd frames, pw frames, reads
+            if (w && c0 + lane < i) {
+#pragma unroll
+                for (uint32_t q = 0; q < kKnPart; ++q) s[q / 3][q % 3] = pp[q];
+            }
+            // (32 read bits at a time: the tests stay 32-bit)
+            for (uint32_t k0 = 0; k0 < kn; k0 += 32) {
+                const uint32_t hx = (uint32_t)(h >> k0), mx = (uint32_t)(x0.m >> k0);
+                const uint32_t rx = (uint32_t)(rw >> k0);
+                const uint32_t cnt = kn - k0 < 32 ? kn - k0 : 32;
+                for (uint32_t kb = 0; kb < cnt; ++kb) {
+                    const bool hb = (hx & (1u << kb)) != 0;
+                    const uint64_t bh = ballot(hb);
+                    const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(k0 + kb)) + lanes_below(bh);
+                    const uint32_t lim = (uint32_t)__builtin_amdgcn_readlane((int)end, (int)(k0 + kb));
+                    const bool eq = have && hb && x0.cb < 4 && ((mx >> kb) & 1u) != 0 && e < lim;
+                    uint32_t fi = 0, fp = 0;
+                    if (eq) fi = kin_frames(ipd[e]), fp = kin_frames(pw[e]);
+                    if ((rx >> kb) & 1u) s[1][0] += fi, s[1][1] += fp, s[1][2] += eq ? 1u : 0u;
+                    else s[0][0] += fi, s[0][1] += fp, s[0][2] += eq ? 1u : 0u;
+                    cur += lane == k0 + kb ? (uint32_t)__builtin_popcountll(bh) : 0u;
+                }
+            }
+            if (!lastw) {
+                if (c0 + lane < i) {
+#pragma unroll
+                    for (uint32_t q = 0; q < kKnPart; ++q) pp[q] = s[q / 3][q % 3];
+                }
+            } else if (x0.cb < 4 && t < z.d.outcap) {
+                uint32_t r[2][3];
+#pragma unroll
+                for (uint32_t d = 0; d < 2; ++d) {
+                    const uint32_t m = s[d][2], dv = m ? m : 1u;
+                    r[d][0] = m ? kin_code((s[d][0] + m / 2) / dv) : 0u;
+                    r[d][1] = m ? kin_code((s[d][1] + m / 2) / dv) : 0u;
+                    r[d][2] = sat8(m);
+                }
+                uint32_t *p = reinterpret_cast<uint32_t *>(kin + (size_t)t * kKnBytes);
+                p[0] = r[0][0] | r[0][1] << 8 | r[0][2] << 16 | r[1][0] << 24;
+                p[1] = r[1][1] | r[1][2] << 8;
+            }
+            base += (uint32_t)__builtin_popcountll(bb);
+            x0 = x1, x1 = x2, h = h1;
+        }
+    }
+}
+
 // SPEC.md §12, the counts of column c (lane = column; v: c is an emitted
 // column, a lane without one counts nothing) split by the strand flags srev (a
 // byte per read of the ZMW, null: all forward): cnt[s][b] the reads of strand s
@@ -3283,12 +3376,20 @@ __device__ __forceinline__ void pileup_col(const Z &z, uint32_t c, bool v, uint3
 // PU (the pileup kernels, KArgs::pile set; pass records and map where their
 // pointers are set): every base written gets its strand pileup record
 // (SPEC.md §12); pc = per strand the bases of the gap-consensus columns emitted
-// since the ZMW's last CCS base (it lives across the rounds, in the caller)
-template <bool PS, bool BM, bool PU>
+// since the ZMW's last CCS base (it lives across the rounds, in the caller);
+// KN (the kinetics kernels, KArgs::kin set; pass records, map and pileup where
+// their pointers are set): every base written gets its kinetics record
+// (SPEC.md §13), from the cursors as the round found them
+template <bool PS, bool BM, bool PU, bool KN = false>
 __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
                                      uint32_t &ol, uint32_t zi, uint32_t (&pc)[2])
 {
-    if constexpr (PU) {
+    if constexpr (KN) {
+        if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
+        if (a.bmap) base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
+        kinetics(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.ksrev + z.d.seg0, a.kipd + a.bmoff[zi],
+                 a.kpw + a.bmoff[zi], a.kin + (size_t)z.d.out_off * kKnBytes);
+    } else if constexpr (PU) {
         if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
         if (a.bmap) base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
     } else if constexpr (BM) {
@@ -3325,7 +3426,7 @@ __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t 
             if (o < z.d.outcap) out[o] = (uint8_t)"ACGT"[cb];
             if (qual && o < z.d.outcap) qual[o] = column_qual(z, c, n);
         }
-        if constexpr (PU) {
+        if (PU || (KN && a.pile)) {
             uint32_t cnt[2][4], cov[2];
             pileup_col(z, c, c < i, n, a.srev ? a.srev + z.d.seg0 : nullptr, cnt, cov);
             // ins: a gap-consensus column gives its bases, a base column takes
@@ -3405,7 +3506,10 @@ __device__ __forceinline__ void write_msa(Z &z, uint32_t ncols, uint32_t n, uint
 // PU: the instance that writes the strand pileup (SPEC.md §12, KArgs::pile
 // set), a kernel of its own for the same reason; in it the pass records and the
 // map are branches on their pointers.
-template <bool RD_HBM, bool PS, bool BM = false, bool PU = false>
+// KN: the instance that writes the consensus kinetics (SPEC.md §13, KArgs::kin
+// set), a kernel of its own again; in it the pass records, the map and the
+// pileup are branches on their pointers.
+template <bool RD_HBM, bool PS, bool BM = false, bool PU = false, bool KN = false>
 __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
 {
     if (blockIdx.x >= a.nzmw) return;
@@ -3460,7 +3564,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
     uint8_t *out = a.out + z.d.out_off;
     uint32_t ol = 0;
     uint32_t pc[2] = {0, 0};  // PU: emit's carry of dropped bases, per strand (zero before the ZMW's first POA call)
-    if (BM || PU ? a.pstat != nullptr : PS) {
+    if (BM || PU || KN ? a.pstat != nullptr : PS) {
         // the pass records accumulate over the emit calls: a slice launched again starts from zero
         uint32_t *ps = a.pstat + (size_t)z.d.seg0 * kPassWords;
         for (uint32_t x = lane; x < n * kPassWords; x += 64) ps[x] = 0;
@@ -3473,7 +3577,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit<PS, BM, PU>(z, ncols, ncols, n, false, out, a, ol, zi, pc);
+            emit<PS, BM, PU, KN>(z, ncols, ncols, n, false, out, a, ol, zi, pc);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3523,7 +3627,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit<PS, BM, PU>(z, i, ncols, n, flag, out, a, ol, zi, pc);
+            emit<PS, BM, PU, KN>(z, i, ncols, n, flag, out, a, ol, zi, pc);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {
@@ -3573,6 +3677,13 @@ ccsx_zmw_kernel_pu(KArgs a)
     zmw_body<false, false, false, true>(a, smem);
 }
 
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_kn(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<false, false, false, false, true>(a, smem);
+}
+
 #ifndef CCSX_RING16  // (solo16 takes LDS-instance slices only: ccsx_gpu.cpp stage_slot)
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
 ccsx_zmw_kernel_hbm(KArgs a)
@@ -3601,6 +3712,13 @@ ccsx_zmw_kernel_hbm_pu(KArgs a)
     extern __shared__ int32_t smem[];
     zmw_body<true, false, false, true>(a, smem);
 }
+
+__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
+ccsx_zmw_kernel_hbm_kn(KArgs a)
+{
+    extern __shared__ int32_t smem[];
+    zmw_body<true, false, false, false, true>(a, smem);
+}
 #endif
 
 }  // namespace CCSX_KCFG
@@ -3624,11 +3742,14 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
 {
     namespace K = ccsx::CCSX_KCFG;
     if (lds_bytes < (uint32_t)K::kLdsFixed * 4u) return hipErrorInvalidValue;
-    // KArgs::pile selects the pileup kernels (which branch on KArgs::bmap and
-    // KArgs::pstat), else KArgs::bmap the map kernels (which branch on
-    // KArgs::pstat), else KArgs::pstat the pass-statistics kernels
-    if (a->bmap && !a->bmoff) return hipErrorInvalidValue;
-    void (*k)(ccsx::KArgs) = a->pile   ? &K::ccsx_zmw_kernel_pu
+    // KArgs::kin selects the kinetics kernels (which branch on KArgs::pile,
+    // KArgs::bmap and KArgs::pstat), else KArgs::pile the pileup kernels (which
+    // branch on KArgs::bmap and KArgs::pstat), else KArgs::bmap the map kernels
+    // (which branch on KArgs::pstat), else KArgs::pstat the pass-statistics kernels
+    if ((a->bmap || a->kin) && !a->bmoff) return hipErrorInvalidValue;
+    if (a->kin && (!a->kipd || !a->kpw || !a->ksrev)) return hipErrorInvalidValue;
+    void (*k)(ccsx::KArgs) = a->kin    ? &K::ccsx_zmw_kernel_kn
+                             : a->pile ? &K::ccsx_zmw_kernel_pu
                              : a->bmap ? &K::ccsx_zmw_kernel_bm
                              : a->pstat ? &K::ccsx_zmw_kernel_ps
                                         : &K::ccsx_zmw_kernel;
@@ -3636,7 +3757,8 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
     if (!a->lds_read_words) return hipErrorInvalidValue;
 #else
     if (!a->lds_read_words)
-        k = a->pile    ? &K::ccsx_zmw_kernel_hbm_pu
+        k = a->kin     ? &K::ccsx_zmw_kernel_hbm_kn
+            : a->pile  ? &K::ccsx_zmw_kernel_hbm_pu
             : a->bmap  ? &K::ccsx_zmw_kernel_hbm_bm
             : a->pstat ? &K::ccsx_zmw_kernel_hbm_ps
                        : &K::ccsx_zmw_kernel_hbm;

@@ -142,6 +142,34 @@ constexpr uint32_t kBmOffMask = (1u << 30) - 1u, kBmMismatch = 1u << 30, kBmIns 
 constexpr uint32_t kPuBytes = 12, kPuGap = 4, kPuIns = 5, kPuFields = 6;
 CCSX_HD inline uint8_t sat8(uint32_t v) { return uint8_t(v > 255u ? 255u : v); }
 
+// Per-base consensus kinetics (SPEC.md §13): eight bytes per CCS base, the
+// layout of ccsx_kinetics (ccsx_gpu.h): per strand (forward reads first) the
+// codes of the mean inter-pulse duration and the mean pulse width over the
+// reads that carry the consensus base, and their number saturating at 255.
+// The 8-bit codec: byte b stands for ((b & 63) << g) + (64 << g) - 64 frames,
+// g = b >> 6; kin_code gives the byte nearest to min(f, kKnMaxFrames), the
+// lower one on a tie.  Integer only: the device and the host share both.
+constexpr uint32_t kKnBytes = 8, kKnMaxFrames = 952;
+// words of a column's partial sums while its reads span several mask words
+// (per strand: ipd frames, pw frames, reads)
+constexpr uint32_t kKnPart = 6;
+// a kinetics strand byte (KArgs::ksrev): bit 0 the segment is reverse, bit 1
+// its ZMW came without kinetics planes (its records are all zero)
+constexpr uint8_t kKnRev = 1, kKnNone = 2;
+CCSX_HD inline uint32_t kin_frames(uint32_t b)
+{
+    const uint32_t g = (b >> 6) & 3u;
+    return ((b & 63u) << g) + (64u << g) - 64u;
+}
+CCSX_HD inline uint8_t kin_code(uint32_t f)
+{
+    if (f > kKnMaxFrames) f = kKnMaxFrames;
+    const uint32_t g = f < 64u ? 0u : f < 192u ? 1u : f < 448u ? 2u : 3u;
+    const uint32_t q = f - ((64u << g) - 64u);
+    // round to the nearest step, a half down; step 64 of a group is code 0 of the next
+    return uint8_t(g * 64u + ((q + (g ? (1u << (g - 1u)) - 1u : 0u)) >> g));
+}
+
 // The extension regions, in order (offsets relative to ZLayout::ext):
 //  * the far rows' slot records (rows with more than four predecessors or one
 //    beyond the DP ring, whose 8-bit cell records carry no tags): per cell the
@@ -290,6 +318,10 @@ struct KArgs {
     const uint64_t *bmoff;     // with bmap: per ZMW, the word offset of its map (the pushed bases of the ZMWs before it)
     uint8_t *pile;             // optional: kPuBytes per CCS byte at (ZmwDesc::out_off + offset) * kPuBytes (SPEC.md §12)
     const uint8_t *srev;       // optional, read with pile: a strand flag per segment at ZmwDesc::seg0 + k (null: all forward)
+    uint8_t *kin;              // optional: kKnBytes per CCS byte at (ZmwDesc::out_off + offset) * kKnBytes (SPEC.md §13); needs bmoff
+    const uint8_t *kipd;       // with kin: an ipd code per pushed base, the map's index space (bmoff[zmw] + the base's entry)
+    const uint8_t *kpw;        // with kin: a pw code per pushed base, likewise
+    const uint8_t *ksrev;      // with kin: a kinetics strand byte (kKnRev | kKnNone) per segment at ZmwDesc::seg0 + k
 };
 
 // phase counters written when KArgs::prof != nullptr

@@ -70,6 +70,7 @@ struct ccsx_synth_batch {
     std::vector<std::vector<uint32_t>> off, len;
     std::vector<std::vector<uint8_t>> rev;  // the strand flags ccsx_prepare gave (ccsx_zmw_in::seg_rev)
     std::vector<ccsx_zmw_in> in;
+    std::vector<std::vector<uint8_t>> ipd, pw;  // ccsx_synth_batch_kinetics
 };
 
 extern "C" {
@@ -113,6 +114,28 @@ ccsx_synth_batch *ccsx_synth_batch_make(uint64_t seed, const uint64_t *holes, co
 }
 
 const ccsx_zmw_in *ccsx_synth_batch_zmws(const ccsx_synth_batch *b) { return b->in.data(); }
+
+void ccsx_synth_batch_kinetics(ccsx_synth_batch *b, uint64_t seed)
+{
+    const size_t n = b->in.size();
+    b->ipd.resize(n);
+    b->pw.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t L = b->seqs[i].size();
+        b->ipd[i].resize(L + 1);
+        b->pw[i].resize(L + 1);
+        uint64_t x = seed ^ (0x9E3779B97F4A7C15ull * (i + 1));
+        for (size_t j = 0; j < L; ++j) {
+            // (splitmix64)
+            uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            z ^= z >> 31;
+            b->ipd[i][j] = uint8_t(z), b->pw[i][j] = uint8_t(z >> 8);
+        }
+        b->in[i].ipd = b->ipd[i].data(), b->in[i].pw = b->pw[i].data();
+    }
+}
 
 void ccsx_synth_batch_free(ccsx_synth_batch *b) { delete b; }
 

@@ -12,6 +12,8 @@
 // tests/golden/host pins all three against the reference's own seqio.h.
 #include "ingest.h"
 
+#include "../ccsx_layout.h"  // kin_code (by path: the sanitizer build has only this directory on its include path)
+
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -467,6 +469,22 @@ void write_bases(const Rec &r, char *dst)
     }
 }
 
+void write_kinetics(const Rec &r, uint8_t *ipd, uint8_t *pw)
+{
+    const uint8_t *src[2] = {r.ip, r.pw};
+    const uint8_t sub[2] = {r.ip_sub, r.pw_sub};
+    uint8_t *dst[2] = {ipd, pw};
+    for (int p = 0; p < 2; ++p) {
+        if (!r.len) continue;
+        if (sub[p] == 'C') {
+            memcpy(dst[p], src[p], r.len);
+        } else {
+            for (uint32_t i = 0; i < r.len; ++i)
+                dst[p][i] = ccsx::kin_code((uint32_t)src[p][2 * (size_t)i] | (uint32_t)src[p][2 * (size_t)i + 1] << 8);
+        }
+    }
+}
+
 namespace {
 
 // ---------------------------------------------------------------- records
@@ -644,6 +662,12 @@ public:
         if (l_qseq < 0 || (size_t)l_qname + n_cigar * 4 + (size_t)(l_qseq + 1) / 2 > data_len) return -4;
         name.assign(data, strnlen(data, l_qname));
         r = Rec{data + l_qname + n_cigar * 4, (uint64_t)(l_qseq + 1) / 2, (uint32_t)l_qseq, kNt16};
+        {
+            // the aux fields behind the qualities: ip / pw as B:C or B:S arrays of l_qseq values
+            const size_t fixed = (size_t)l_qname + n_cigar * 4 + (size_t)(l_qseq + 1) / 2;
+            if (data_len - fixed >= (size_t)l_qseq)
+                aux_kinetics(reinterpret_cast<const uint8_t *>(data) + fixed + l_qseq, data_len - fixed - (size_t)l_qseq, r);
+        }
         keep = c_.block();
         c_.pos += (size_t)block_len;
         return l_qseq;
@@ -652,6 +676,66 @@ public:
 private:
     Cursor c_;
     bool header_done_ = false, dead_ = false;
+    // Walk the n aux bytes at a (tag[2] type value ...) for the ip and pw
+    // arrays of r.len values; every length is checked against n before a byte
+    // is read, and a field that runs past the record drops both.
+    static void aux_kinetics(const uint8_t *a, size_t n, Rec &r)
+    {
+        size_t q = 0;
+        bool bad = false;
+        while (q < n) {
+            if (n - q < 3) {
+                bad = true;
+                break;
+            }
+            const uint8_t t0 = a[q], t1 = a[q + 1], ty = a[q + 2];
+            q += 3;
+            size_t sz = 0;
+            if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+            else if (ty == 's' || ty == 'S') sz = 2;
+            else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+            else if (ty == 'Z' || ty == 'H') {
+                const void *e = memchr(a + q, 0, n - q);
+                if (!e) {
+                    bad = true;
+                    break;
+                }
+                q = (size_t)(static_cast<const uint8_t *>(e) - a) + 1;
+                continue;
+            } else if (ty == 'B') {
+                if (n - q < 5) {
+                    bad = true;
+                    break;
+                }
+                const uint8_t sub = a[q];
+                uint32_t cnt;
+                memcpy(&cnt, a + q + 1, 4);
+                q += 5;
+                const size_t es = sub == 'c' || sub == 'C' ? 1 : sub == 's' || sub == 'S' ? 2
+                                  : sub == 'i' || sub == 'I' || sub == 'f' ? 4 : 0;
+                if (!es || (uint64_t)cnt * es > n - q) {
+                    bad = true;
+                    break;
+                }
+                const bool ip = t0 == 'i' && t1 == 'p', pw = t0 == 'p' && t1 == 'w';
+                if ((ip || pw) && cnt == r.len && (sub == 'C' || sub == 'S')) {
+                    if (ip) r.ip = a + q, r.ip_sub = sub;
+                    else r.pw = a + q, r.pw_sub = sub;
+                }
+                q += (size_t)cnt * es;
+                continue;
+            } else {
+                bad = true;
+                break;
+            }
+            if (n - q < sz) {
+                bad = true;
+                break;
+            }
+            q += sz;
+        }
+        if (bad || !r.has_kinetics()) r.ip = r.pw = nullptr, r.ip_sub = r.pw_sub = 0;
+    }
     // n bytes available at pos (fetching more input as needed)
     bool avail(size_t n)
     {

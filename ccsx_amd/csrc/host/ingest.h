@@ -32,6 +32,14 @@ struct Rec {
     uint64_t span = 0;          // bytes of the region
     uint32_t len = 0;           // bases (after kseq's line rules / BAM l_qseq)
     uint8_t kind = 0;           // kAscii1, kAsciiLines or kNt16
+    // BAM: the values of the record's ip / pw aux arrays (SPEC.md §13), len of
+    // them each, and their subtype: 'C' the 8-bit codes, 'S' frames as
+    // little-endian uint16 (possibly unaligned), 0 none.  A record has both or
+    // neither: an absent tag, a count other than len, another subtype or an
+    // aux field running past the record leaves it without kinetics.
+    const uint8_t *ip = nullptr, *pw = nullptr;
+    uint8_t ip_sub = 0, pw_sub = 0;
+    bool has_kinetics() const { return ip_sub != 0 && pw_sub != 0; }
 };
 enum : uint8_t { kAscii1 = 0, kAsciiLines = 1, kNt16 = 2 };
 
@@ -39,6 +47,9 @@ enum : uint8_t { kAscii1 = 0, kAsciiLines = 1, kNt16 = 2 };
 void append_bases(const Rec &r, std::string &out);
 // ... written to dst (r.len bytes)
 void write_bases(const Rec &r, char *dst);
+// the kinetics codes of r (has_kinetics), r.len bytes each, in the record's
+// base order: 'C' values as they are, 'S' frames encoded with kin_code
+void write_kinetics(const Rec &r, uint8_t *ipd, uint8_t *pw);
 
 struct ZmwRef {
     std::string movie, hole;

@@ -125,6 +125,9 @@ struct Zmw {
     std::vector<ccsx_pass_stat> pst;  // -r: one record per segment (SPEC.md section 10)
     std::string paf;          // -a: the PAF lines of its segments (SPEC.md section 11)
     std::string sites;        // -s: the lines of its discordant sites (SPEC.md section 12)
+    std::vector<uint8_t> kin;  // -k: the ipd codes of its bases, then the pw codes, parallel to seqs (empty: a subread lacks them)
+    std::string kinline;      // -k: its SAM line (SPEC.md section 13)
+    bool kin_arrays = false;  // -k: ... carries the four arrays
     int32_t status = 0;
     std::vector<uint32_t> bp;  // -v >= 3: (breakpoint, MSA columns) per shredding round
 };
@@ -171,6 +174,7 @@ int usage()
             "-r     <file>  Pass report (tab-separated): per subread, its match/mismatch/ins/del counts against the CCS, the CCS stretch it covers, identity \n"
             "-a     <file>  Subread-to-CCS alignments (PAF, cg:Z: with =/X/I/D): per subread, where its bases lie in the CCS by the alignment the CCS was called from \n"
             "-s     <file>  Strand-discordant sites (tab-separated): per CCS position whose forward and reverse subreads call different bases (or base against gap), the two calls and the per-strand A/C/G/T/gap/ins counts \n"
+            "-k     <file>  Consensus kinetics (unaligned SAM; BAM input only): per CCS read its bases, np/fn/rn and, from the subreads' ip/pw tags, the per-strand mean inter-pulse duration and pulse width per base as fi/fp/ri/rp B:C arrays \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
             "\n"
@@ -197,7 +201,7 @@ int usage()
 // input blocks (the copy step 0 of the reference makes, main.c:674-685), then
 // ccs_prepare + strand flip (the CPU half of step 1, main.c:520-536, with its
 // -v output)
-void prepare_chunk(Chunk &ch, int nthreads, int verbose)
+void prepare_chunk(Chunk &ch, int nthreads, int verbose, bool kinetics)
 {
     std::vector<Zmw> &zs = ch.zs;
     // each ZMW's bases at its offset in the chunk's arena
@@ -220,6 +224,20 @@ void prepare_chunk(Chunk &ch, int nthreads, int verbose)
                 z.lens[k] = r.len;
                 o += r.len;
             }
+            if (kinetics) {
+                // -k: the two code planes beside the bases, where every subread has them
+                bool have = true;
+                for (const ccsx_ingest::Rec &r : z.ref.recs) have = have && r.has_kinetics();
+                if (have) {
+                    z.kin.resize(2 * o + 2);
+                    size_t q = 0;
+                    for (const ccsx_ingest::Rec &r : z.ref.recs) {
+                        ccsx_ingest::write_kinetics(r, z.kin.data() + q, z.kin.data() + o + q);
+                        q += r.len;
+                    }
+                }
+            }
+            const size_t total = o;
             ccsx_ingest::ZmwRef().recs.swap(z.ref.recs);
             std::vector<std::shared_ptr<ccsx_ingest::Block>>().swap(z.ref.keep);
             const uint32_t n = (uint32_t)z.lens.size();
@@ -235,6 +253,12 @@ void prepare_chunk(Chunk &ch, int nthreads, int verbose)
             if (verbose > 1) msg += "poa begin " + z.hole + "\n";
             for (uint32_t l = 0; l < ns; ++l) {
                 if (z.seg_rev[l]) ccsx_revcomp(&z.seqs[z.seg_off[l]], z.seg_len[l]);
+                if (z.seg_rev[l] && !z.kin.empty()) {
+                    // (ccsx_prepare_apply_kin: the values stay with their bases)
+                    uint8_t *a = z.kin.data() + z.seg_off[l], *b = z.kin.data() + total + z.seg_off[l];
+                    std::reverse(a, a + z.seg_len[l]);
+                    std::reverse(b, b + z.seg_len[l]);
+                }
                 if (verbose) {
                     // main.c:477-479 / 533-535
                     char h[160];
@@ -468,10 +492,11 @@ int main(int argc, char **argv)
     const char *report_path = nullptr;  // -r
     const char *paf_path = nullptr;     // -a
     const char *site_path = nullptr;    // -s
+    const char *kin_path = nullptr;     // -k
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -481,6 +506,7 @@ int main(int argc, char **argv)
         case 'r': report_path = optarg; break;
         case 'a': paf_path = optarg; break;
         case 's': site_path = optarg; break;
+        case 'k': kin_path = optarg; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -496,6 +522,10 @@ int main(int argc, char **argv)
         case 'j': nthreads = atoi(optarg); break;
         default: return usage();
         }
+    }
+    if (kin_path && !isbam) {
+        fprintf(stderr, "Error! -k needs BAM input (the kinetics are the subreads' ip / pw tags): not with -A\n");
+        return 1;
     }
     // main.c:802-826
     const char *in_path = "-";
@@ -538,6 +568,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
+    FILE *fp_kin = kin_path ? fopen(kin_path, "w") : nullptr;
+    if (kin_path && !fp_kin) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    if (fp_kin) fprintf(fp_kin, "@HD\tVN:1.6\tSO:unknown\n");
     if (fp_rep) fprintf(fp_rep, "#name\tpass\tsbeg\tslen\tmatch\tmismatch\tins\tdel\tcbeg\tcend\tidentity\n");
     // step 1 pipelined per context (ccsx_gpu_submit / ccsx_gpu_collect: the
     // next batch is launched before the previous one is collected);
@@ -630,6 +666,7 @@ int main(int argc, char **argv)
         for (size_t i = 0; i < f.b.idx.size(); ++i) {
             const Zmw &z = ch.zs[f.b.idx[i]];
             f.in[i] = ccsx_zmw_in{z.seqs, z.seg_off.data(), z.seg_len.data(), (uint32_t)z.seg_len.size(), z.seg_rev.data()};
+            if (!z.kin.empty()) f.in[i].ipd = z.kin.data(), f.in[i].pw = z.kin.data() + (z.kin.size() - 2) / 2;
             if (!fault_hole.empty() && z.hole == fault_hole) ccsx_gpu_set_fault(ctx[w], (int64_t)i);
         }
         f.t0 = now_ms();
@@ -638,7 +675,7 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
-        bool qfail = false;  // -q / -r / -a / -s: the batch's qualities, pass records, maps or pileups are missing (a context error)
+        bool qfail = false;  // -q / -r / -a / -s / -k: the batch's qualities, pass records, maps, pileups or kinetics are missing (a context error)
         if (r == 0 || r == -2) {
             // -2: some ZMWs failed on the device, the rest are valid
             uint64_t cells = 0;
@@ -717,6 +754,43 @@ int main(int argc, char **argv)
                                  b[3], b[4], b[5]);
                         z.sites += z.movie + "/" + z.hole + line;
                     }
+                }
+                if (fp_kin && !f.out[i].status && f.out[i].len) {
+                    // the ZMW's SAM line; the four arrays only where it came with kinetics
+                    const ccsx_kinetics *kr = nullptr;
+                    uint32_t kl = 0;
+                    if (ccsx_gpu_kinetics(ctx[w], f.slot, i, &kr, &kl) != 0 || kl != f.out[i].len) {
+                        qfail = true;
+                        break;
+                    }
+                    size_t nrev = 0;
+                    for (uint8_t v : z.seg_rev) nrev += v != 0;
+                    char num[96];
+                    std::string &s = z.kinline;
+                    s = z.movie + "/" + z.hole + "/ccs\t4\t*\t0\t255\t*\t*\t0\t0\t";
+                    s.append(f.out[i].ccs, f.out[i].len);
+                    s += '\t';
+                    if (fastq) s += z.qual;
+                    else s += '*';
+                    snprintf(num, sizeof num, "\tnp:i:%zu", z.seg_len.size());
+                    s += num;
+                    if (fastq) {
+                        snprintf(num, sizeof num, "\trq:f:%.6f", z.rq);
+                        s += num;
+                    }
+                    snprintf(num, sizeof num, "\tfn:i:%zu\trn:i:%zu", z.seg_rev.size() - nrev, nrev);
+                    s += num;
+                    z.kin_arrays = !z.kin.empty();
+                    if (z.kin_arrays) {
+                        const long n = ccsx_kinetics_tags(kr, kl, nullptr, 0);
+                        const size_t at = s.size() + 1;
+                        s += '\t';
+                        s.resize(at + (size_t)n + 1);
+                        (void)ccsx_kinetics_tags(kr, kl, &s[at], (size_t)n + 1);
+                        s.resize(at + (size_t)n);
+                    }
+                    s += '\n';
+                    std::vector<uint8_t>().swap(z.kin);
                 }
                 const uint32_t *lg;
                 uint32_t nr = 0;
@@ -915,6 +989,7 @@ int main(int argc, char **argv)
             if (fp_rep) ccsx_gpu_set_pass_stats(ctx[i], 1);
             if (fp_paf) ccsx_gpu_set_base_map(ctx[i], 1);
             if (fp_site) ccsx_gpu_set_pileup(ctx[i], 1);
+            if (fp_kin) ccsx_gpu_set_kinetics(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
@@ -942,6 +1017,7 @@ int main(int argc, char **argv)
 
     // step 2: ordered output (main.c:707-717)
     size_t nfail = 0;
+    size_t nokin = 0;  // -k: lines written without the arrays (a subread lacked ip / pw)
     // the last chunk written stays referenced here and the ones before it are
     // freed on a thread of their own: freeing a chunk (its per-ZMW vectors and
     // strings, the input blocks it holds) takes up to a few hundred ms, which
@@ -985,6 +1061,10 @@ int main(int argc, char **argv)
                         }
                     if (fp_paf) fwrite(z.paf.data(), 1, z.paf.size(), fp_paf);
                     if (fp_site) fwrite(z.sites.data(), 1, z.sites.size(), fp_site);
+                    if (fp_kin) {
+                        if (!z.kin_arrays) ++nokin;
+                        fwrite(z.kinline.data(), 1, z.kinline.size(), fp_kin);
+                    }
                 }
             }
             if (timing) fprintf(stderr, "[ccsx] chunk %zu written at %.0f ms\n", ch->id, now_ms());
@@ -1002,7 +1082,7 @@ int main(int argc, char **argv)
         std::vector<Zmw> &zs = ch->zs;
         const size_t id = ch->id;
         const double t0 = ch->t_read0, t1 = ch->t_read1;
-        prepare_chunk(*ch, nthreads, verbose);
+        prepare_chunk(*ch, nthreads, verbose, fp_kin != nullptr);
         // the chunk's bases are in its arena: its input pages go (a mapped
         // file is unmapped behind the reader instead of all at the exit)
         if (input_release) rd->release(ch->input_hi);
@@ -1061,6 +1141,7 @@ int main(int argc, char **argv)
         if (fp_rep) werr = (ferror(fp_rep) || fclose(fp_rep) != 0) || werr;
         if (fp_paf) werr = (ferror(fp_paf) || fclose(fp_paf) != 0) || werr;
         if (fp_site) werr = (ferror(fp_site) || fclose(fp_site) != 0) || werr;
+        if (fp_kin) werr = (ferror(fp_kin) || fclose(fp_kin) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1089,6 +1170,7 @@ int main(int argc, char **argv)
                     (unsigned long long)cells_total.load(),
                     std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count());
         if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
+        if (fp_kin) fprintf(stderr, "[ccsx] %zu ZMWs without kinetics: their -k lines carry no fi/fp/ri/rp arrays\n", nokin);
         fflush(stderr);
         std::_Exit(werr ? 1 : 0);
     }
@@ -1103,6 +1185,7 @@ int main(int argc, char **argv)
     if (fp_rep) (void)fclose(fp_rep);
     if (fp_paf) (void)fclose(fp_paf);
     if (fp_site) (void)fclose(fp_site);
+    if (fp_kin) (void)fclose(fp_kin);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

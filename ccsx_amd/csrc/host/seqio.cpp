@@ -15,6 +15,7 @@ struct ccsx_reader {
     ccsx_ingest::ZmwRef z;
     std::string seqs;
     std::vector<uint32_t> lens;
+    std::vector<uint8_t> ipd, pw;
 };
 
 extern "C" {
@@ -42,6 +43,25 @@ int ccsx_reader_next(ccsx_reader *r, const char **movie, const char **hole, cons
         }
     }
     *movie = r->z.movie.c_str(), *hole = r->z.hole.c_str(), *seqs = r->seqs.data(), *lens = r->lens.data();
+    return l;
+}
+
+int ccsx_reader_next_kin(ccsx_reader *r, const char **movie, const char **hole, const char **seqs, const uint32_t **lens,
+                         const uint8_t **ipd, const uint8_t **pw)
+{
+    const int l = ccsx_reader_next(r, movie, hole, seqs, lens);
+    *ipd = *pw = nullptr;
+    if (l <= 0) return l;
+    for (const auto &x : r->z.recs)
+        if (!x.has_kinetics()) return l;
+    r->ipd.resize(r->seqs.size() + 1);
+    r->pw.resize(r->seqs.size() + 1);
+    size_t o = 0;
+    for (const auto &x : r->z.recs) {
+        ccsx_ingest::write_kinetics(x, r->ipd.data() + o, r->pw.data() + o);
+        o += x.len;
+    }
+    *ipd = r->ipd.data(), *pw = r->pw.data();
     return l;
 }
 

@@ -1,6 +1,6 @@
 // side_out.h -- the engine's optional per-ZMW outputs beside the CCS (the
-// "side outputs": qualities, pass records, subread-to-CCS map, strand pileup;
-// SPEC.md §9-§12), each described once: what it costs, where its plane lies in
+// "side outputs": qualities, pass records, subread-to-CCS map, strand pileup,
+// consensus kinetics; SPEC.md §9-§13), each described once: what it costs, where its plane lies in
 // a fetched slice, how a batch's results are gathered and how an accessor finds
 // them.  No HIP here: ccsx_gpu.cpp owns the device side (DESIGN.md §14 lists
 // what a further output has to touch); tools/host_sanitize.cpp drives this file
@@ -15,37 +15,44 @@
 
 namespace ccsx {
 
-enum SideOut : int { kSideQual = 0, kSidePass, kSideMap, kSidePile, kSideCount };
+enum SideOut : int { kSideQual = 0, kSidePass, kSideMap, kSidePile, kSideKin, kSideCount };
 typedef uint32_t SideMask;  // bit o: output o is on
 constexpr SideMask side_bit(int o) { return SideMask(1) << o; }
 constexpr SideMask kSideAll = side_bit(kSideCount) - 1;
 
 static_assert(sizeof(ccsx_pass_stat) == kPassWords * 4, "ccsx_pass_stat is the kernel's record");
 static_assert(sizeof(ccsx_pileup) == kPuBytes, "ccsx_pileup is the kernel's record");
+static_assert(sizeof(ccsx_kinetics) == kKnBytes, "ccsx_kinetics is the kernel's record");
 
 // One row per output.  Its plane takes per_slab bytes per byte of the output
 // slab + per_seg per segment + per_base per pushed base; flags_per_seg more
-// bytes per segment are an input of its own (the pileup's strand flags), copied
-// back behind the plane.
+// bytes per segment are an input of its own (the pileup's strand flags, the
+// kinetics' strand bytes), copied back behind the plane; in_per_base more bytes
+// per pushed base are an input that stays on the device (the kinetics' two code
+// planes): they count in every device size (side_need_of), not in the fetched
+// slice.
 struct SideInfo {
-    uint32_t per_slab, per_seg, per_base, flags_per_seg;
+    uint32_t per_slab, per_seg, per_base, flags_per_seg, in_per_base;
     bool in_out;         // the plane lies directly behind the CCS plane in the output buffer and is
                          // fetched with it, at the CCS's offsets (else: a device buffer of its own)
     const char *off;     // the accessor's refusal of a batch that ran without the output
     const char *failed;  // ... and of a ZMW without a result (null: it reads as length 0)
 };
 constexpr SideInfo kSide[kSideCount] = {
-    {1, 0, 0, 0, true, "that batch ran with quality off (ccsx_gpu_set_quality)", nullptr},
-    {0, kPassWords * 4, 0, 0, false, "that batch ran with pass statistics off (ccsx_gpu_set_pass_stats)",
+    {1, 0, 0, 0, 0, true, "that batch ran with quality off (ccsx_gpu_set_quality)", nullptr},
+    {0, kPassWords * 4, 0, 0, 0, false, "that batch ran with pass statistics off (ccsx_gpu_set_pass_stats)",
      "that ZMW failed: it has no pass statistics"},
-    {0, 0, 4, 0, false, "that batch ran with the base map off (ccsx_gpu_set_base_map)",
+    {0, 0, 4, 0, 0, false, "that batch ran with the base map off (ccsx_gpu_set_base_map)",
      "that ZMW failed: it has no base map"},
-    {kPuBytes, 0, 0, 1, false, "that batch ran with the pileup off (ccsx_gpu_set_pileup)",
+    {kPuBytes, 0, 0, 1, 0, false, "that batch ran with the pileup off (ccsx_gpu_set_pileup)",
      "that ZMW failed: it has no pileup"},
+    {kKnBytes, 0, 0, 1, 2, false, "that batch ran with kinetics off (ccsx_gpu_set_kinetics)",
+     "that ZMW failed: it has no kinetics"},
 };
 
-// Bytes of output o's plane and, with its flags, the bytes it adds to a ZMW
-// (its output slab, segments, pushed bases) or to a slice (their sums)
+// Bytes of output o's plane and, with its flags, the bytes it takes in a
+// fetched slice; with its device-only input (side_input) the bytes it adds to a
+// ZMW (its output slab, segments, pushed bases) or to a slice (their sums)
 inline uint64_t side_plane(int o, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
     return kSide[o].per_slab * slab + kSide[o].per_seg * nseg + kSide[o].per_base * nbase;
@@ -54,11 +61,20 @@ inline uint64_t side_bytes(int o, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
     return side_plane(o, slab, nseg, nbase) + kSide[o].flags_per_seg * nseg;
 }
+inline uint64_t side_input(int o, uint64_t nbase) { return uint64_t(kSide[o].in_per_base) * nbase; }
 inline uint64_t side_bytes_of(SideMask m, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
     uint64_t b = 0;
     for (int o = 0; o < kSideCount; ++o)
         if (m & side_bit(o)) b += side_bytes(o, slab, nseg, nbase);
+    return b;
+}
+// ... and what the outputs of m add to the device bytes of a ZMW or a slice
+inline uint64_t side_need_of(SideMask m, uint64_t slab, uint64_t nseg, uint64_t nbase)
+{
+    uint64_t b = side_bytes_of(m, slab, nseg, nbase);
+    for (int o = 0; o < kSideCount; ++o)
+        if (m & side_bit(o)) b += side_input(o, nbase);
     return b;
 }
 
@@ -89,7 +105,8 @@ struct SideLayout {
     }
 };
 // (an in_out plane behind an aligned one would not be fetched with the CCS)
-static_assert(kSide[0].in_out && !kSide[1].in_out && !kSide[2].in_out && !kSide[3].in_out, "in_out planes come first");
+static_assert(kSide[0].in_out && !kSide[1].in_out && !kSide[2].in_out && !kSide[3].in_out && !kSide[4].in_out,
+              "in_out planes come first");
 
 // One ZMW's results where they lie, in a fetched slice or a gathered batch; the
 // planes of outputs that are off are null
@@ -103,6 +120,7 @@ struct SideRec {
     const uint32_t *seg_len = nullptr;  // with map: nseg lengths
     const uint32_t *seg_at = nullptr;   // with map: nseg word offsets into map (null: the lengths' running sum)
     const ccsx_pileup *pile = nullptr;  // len records
+    const ccsx_kinetics *kin = nullptr;  // len records
     // segment k of the map
     const uint32_t *map_seg(uint32_t k) const
     {
@@ -141,16 +159,17 @@ struct SideView {
             r.seg_len = seg_len + d.seg0;
         }
         if (lay->has(kSidePile)) r.pile = reinterpret_cast<const ccsx_pileup *>(h_out + lay->off[kSidePile]) + d.out_off;
+        if (lay->has(kSideKin)) r.kin = reinterpret_cast<const ccsx_kinetics *>(h_out + lay->off[kSideKin]) + d.out_off;
         return r;
     }
 };
 
 // The gathered results of one ccsx_gpu_run call or one collected batch, per ZMW
 // of the call in input order: the CCS strings and, for every output of `mask`,
-// its payload.  Qualities and pileup records lie at the CCS's offsets.
+// its payload.  Qualities, pileup and kinetics records lie at the CCS's offsets.
 struct Gathered {
     struct At {
-        uint64_t ccs = 0, pass = 0, map = 0, seg = 0;  // offsets into arena (qual, pile), pass, map, seg_len (seg_at)
+        uint64_t ccs = 0, pass = 0, map = 0, seg = 0;  // offsets into arena (qual, pile, kin), pass, map, seg_len (seg_at)
         uint32_t len = 0, nseg = 0;
         bool ok = false;
     };
@@ -160,6 +179,7 @@ struct Gathered {
     std::vector<uint32_t> pass, map;
     std::vector<uint32_t> seg_len, seg_at;  // per gathered segment of the map: entries, word offset in its ZMW's map
     std::vector<ccsx_pileup> pile;
+    std::vector<ccsx_kinetics> kin;
     SideMask enabled() const { return mask; }
     bool has(int o) const { return (mask & side_bit(o)) != 0; }
     size_t size() const { return at.size(); }
@@ -167,7 +187,7 @@ struct Gathered {
     {
         mask = m;
         at.assign(nz, At{});
-        arena.clear(), qual.clear(), pass.clear(), map.clear(), seg_len.clear(), seg_at.clear(), pile.clear();
+        arena.clear(), qual.clear(), pass.clear(), map.clear(), seg_len.clear(), seg_at.clear(), pile.clear(), kin.clear();
     }
     // one growth per slice of `add` CCS bytes, not one per ZMW's append (~150
     // MB for a 10k-ZMW slice of 15 kb inserts)
@@ -200,6 +220,7 @@ struct Gathered {
             map.insert(map.end(), r.map, r.map + tot);
         }
         if (has(kSidePile)) pile.insert(pile.end(), r.pile, r.pile + r.len);
+        if (has(kSideKin)) kin.insert(kin.end(), r.kin, r.kin + r.len);
     }
     // ZMW g is reported as failed after all: without a result in every output
     void drop(size_t g) { at[g].ok = false, at[g].len = 0; }
@@ -215,6 +236,7 @@ struct Gathered {
         if (has(kSidePass)) r.pass = pass.data() + a.pass;
         if (has(kSideMap)) r.map = map.data() + a.map, r.seg_len = seg_len.data() + a.seg, r.seg_at = seg_at.data() + a.seg;
         if (has(kSidePile)) r.pile = pile.data() + a.ccs;
+        if (has(kSideKin)) r.kin = kin.data() + a.ccs;
         return r;
     }
 };

@@ -31,19 +31,23 @@ EXPORTS = {
                    "ccsx_gpu_set_shred_read_cap", "ccsx_gpu_set_mem_frac", "ccsx_gpu_set_mem_wait",
                    "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
                    "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats",
-                   "ccsx_gpu_set_base_map", "ccsx_gpu_base_map", "ccsx_gpu_set_pileup", "ccsx_gpu_pileup"],
+                   "ccsx_gpu_set_base_map", "ccsx_gpu_base_map", "ccsx_gpu_set_pileup", "ccsx_gpu_pileup",
+                   "ccsx_gpu_set_kinetics", "ccsx_gpu_kinetics"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
                     "ccsx_map_cigar", "ccsx_pileup_call",
+                    "ccsx_prepare_apply_kin", "ccsx_kin_frames", "ccsx_kin_code", "ccsx_kinetics_tags",
+                    "ccsx_synth_batch_kinetics",
                     "ccsx_synth_batch_make", "ccsx_synth_batch_zmws", "ccsx_synth_batch_free"],
-    "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_close"],
+    "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_next_kin", "ccsx_reader_close"],
 }
 
 
 class ZmwIn(C.Structure):
     _fields_ = [("seqs", C.c_char_p), ("seg_off", C.POINTER(C.c_uint32)), ("seg_len", C.POINTER(C.c_uint32)),
-                ("nseg", C.c_uint32), ("seg_rev", C.POINTER(C.c_uint8))]
+                ("nseg", C.c_uint32), ("seg_rev", C.POINTER(C.c_uint8)),
+                ("ipd", C.POINTER(C.c_uint8)), ("pw", C.POINTER(C.c_uint8))]
 
 
 class ZmwOut(C.Structure):
@@ -132,6 +136,21 @@ def lib() -> C.CDLL:
         L.ccsx_gpu_set_pileup.argtypes = [C.c_void_p, C.c_int]
         L.ccsx_gpu_pileup.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.ccsx_pileup_call.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "ccsx_gpu_set_kinetics"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_gpu_set_kinetics.argtypes = [C.c_void_p, C.c_int]
+            L.ccsx_gpu_kinetics.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+            L.ccsx_kin_frames.argtypes = [C.c_uint8]
+            L.ccsx_kin_frames.restype = C.c_uint32
+            L.ccsx_kin_code.argtypes = [C.c_uint32]
+            L.ccsx_kin_code.restype = C.c_uint8
+            L.ccsx_kinetics_tags.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+            L.ccsx_kinetics_tags.restype = C.c_long
+            L.ccsx_prepare_apply_kin.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32,
+                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+            L.ccsx_prepare_apply_kin.restype = C.c_uint32
+            L.ccsx_synth_batch_kinetics.argtypes = [C.c_void_p, C.c_uint64]
+            L.ccsx_reader_next_kin.argtypes = [C.c_void_p] + [C.POINTER(C.c_char_p)] * 2 + [
+                C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.ccsx_revcomp.argtypes = [C.c_char_p, C.c_uint32]
         L.ccsx_prepare.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
@@ -198,15 +217,37 @@ def synth_zmw(seed: int, hole: int, L: int, passes: int):
 class Prepared:
     """One ZMW after ccs_prepare + strand flip: segments are slices of seqs;
     rev = ccs_prepare's strand flag per segment (None: all forward), read by the
-    engine only with the strand pileup on."""
+    engine only with the strand pileup or the kinetics on; ipd / pw = one 8-bit
+    kinetics code per byte of seqs in the orientation the segments are pushed in
+    (SPEC.md §13; None: the ZMW has none), read only with the kinetics on."""
     seqs: bytes
     offs: np.ndarray
     lens: np.ndarray
     rev: np.ndarray | None = None
+    ipd: bytes | None = None
+    pw: bytes | None = None
 
 
-def prepare(subreads: list[bytes]) -> Prepared:
-    """ccs_prepare (main.c:344-453) + in-place reverse complement of reverse segments."""
+def prepare(subreads: list[bytes], ipd=None, pw=None) -> Prepared:
+    """ccs_prepare (main.c:344-453) + in-place reverse complement of reverse
+    segments; with ipd and pw (one bytes of codes per subread, parallel to its
+    bases) also their reversal over each reverse segment (ccsx_prepare_apply_kin)."""
+    if ipd is not None or pw is not None:
+        if ipd is None or pw is None or [len(x) for x in ipd] != [len(s) for s in subreads] or \
+                [len(x) for x in pw] != [len(s) for s in subreads]:
+            raise ValueError("ipd and pw need one code per base of every subread")
+        seqs = b"".join(subreads)
+        buf = C.create_string_buffer(seqs, len(seqs) + 1)
+        bi = C.create_string_buffer(b"".join(bytes(x) for x in ipd), len(seqs) + 1)
+        bp = C.create_string_buffer(b"".join(bytes(x) for x in pw), len(seqs) + 1)
+        lens = _u32([len(s) for s in subreads])
+        n = len(subreads)
+        so, sl = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        rv = np.zeros(max(n, 1), dtype=np.uint8)
+        ns = lib().ccsx_prepare_apply_kin(buf, bi, bp, _p32(lens), n, _p32(so), _p32(sl),
+                                          rv.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return Prepared(buf.raw[:len(seqs)], so[:ns].copy(), sl[:ns].copy(), rv[:ns].copy(),
+                        bi.raw[:len(seqs)], bp.raw[:len(seqs)])
     seqs = b"".join(subreads)
     buf = C.create_string_buffer(seqs, len(seqs) + 1)
     lens = _u32([len(s) for s in subreads])
@@ -299,6 +340,28 @@ def map_cigar(m):
     return d
 
 
+def kin_frames(code: int) -> int:
+    """ccsx_kin_frames: the frames an 8-bit kinetics code stands for (SPEC.md §13)."""
+    return int(lib().ccsx_kin_frames(code))
+
+
+def kin_code(frames: int) -> int:
+    """ccsx_kin_code: the code nearest to min(frames, 952), the lower on a tie."""
+    return int(lib().ccsx_kin_code(frames))
+
+
+def kinetics_tags(recs) -> str:
+    """ccsx_kinetics_tags: the fi / fp / ri / rp SAM array tags (tab-separated)
+    of a ZMW's kinetics records (Engine.kinetics, uint8 [len, 8])."""
+    r = np.ascontiguousarray(np.asarray(recs, dtype=np.uint8).reshape(-1, 8))
+    L = lib()
+    need = L.ccsx_kinetics_tags(r.ctypes.data, len(r), None, 0)
+    buf = C.create_string_buffer(need + 1)
+    if L.ccsx_kinetics_tags(r.ctypes.data, len(r), buf, need + 1) != need:
+        raise RuntimeError("ccsx_kinetics_tags: inconsistent length")
+    return buf.value.decode()
+
+
 def pileup_call(rec, strand: int) -> int:
     """ccsx_pileup_call: the call of strand 0 (forward) / 1 (reverse) / 2 (both)
     from one 12-byte pileup record (Engine.pileup; SPEC.md §12): 0..3 a base, 4
@@ -307,11 +370,13 @@ def pileup_call(rec, strand: int) -> int:
     return int(lib().ccsx_pileup_call(r.ctypes.data, strand))
 
 
-def read_calls(path: str, is_bam: bool = False):
+def read_calls(path: str, is_bam: bool = False, kinetics: bool = False):
     """Yield every ccsx_reader_next result the way main.c step 0 drives
     kseq_zmw_read (main.c:658-697): (n, movie, hole, [subreads]) for a ZMW,
     (-1, None, None, None) for each -1; after a -1 the next chunk reads on,
-    and the input ends at the first chunk that yields no ZMW."""
+    and the input ends at the first chunk that yields no ZMW.  kinetics: read
+    with ccsx_reader_next_kin and yield two more fields per ZMW, the ipd and pw
+    codes per subread (lists of bytes), or None, None where the ZMW has none."""
     L = lib()
     r = L.ccsx_reader_open(path.encode(), 1 if is_bam else 0)
     if not r:
@@ -323,9 +388,13 @@ def read_calls(path: str, is_bam: bool = False):
         while True:
             got = 0
             while True:
-                n = L.ccsx_reader_next(r, C.byref(mv), C.byref(hl), C.byref(sq), C.byref(ln))
+                ki, kp = C.c_void_p(), C.c_void_p()
+                if kinetics:
+                    n = L.ccsx_reader_next_kin(r, C.byref(mv), C.byref(hl), C.byref(sq), C.byref(ln), C.byref(ki), C.byref(kp))
+                else:
+                    n = L.ccsx_reader_next(r, C.byref(mv), C.byref(hl), C.byref(sq), C.byref(ln))
                 if n < 0:
-                    yield n, None, None, None
+                    yield (n, None, None, None, None, None) if kinetics else (n, None, None, None)
                     break
                 got += 1
                 lens = [ln[i] for i in range(n)]
@@ -334,6 +403,19 @@ def read_calls(path: str, is_bam: bool = False):
                 for x in lens:
                     subs.append(raw[o:o + x])
                     o += x
+                if kinetics:
+                    planes = []
+                    for p in (ki, kp):
+                        if p.value:
+                            rawk, o, per = C.string_at(p, sum(lens)), 0, []
+                            for x in lens:
+                                per.append(rawk[o:o + x])
+                                o += x
+                            planes.append(per)
+                        else:
+                            planes.append(None)
+                    yield n, mv.value.decode(), hl.value.decode(), subs, planes[0], planes[1]
+                    continue
                 yield n, mv.value.decode(), hl.value.decode(), subs
             if not got:
                 break
@@ -341,11 +423,13 @@ def read_calls(path: str, is_bam: bool = False):
         L.ccsx_reader_close(r)
 
 
-def read_zmws(path: str, is_bam: bool = False):
-    """Yield (movie, hole, [subreads]) per ZMW, as the CLI's step 0 sees them."""
-    for n, movie, hole, subs in read_calls(path, is_bam):
-        if n >= 0:
-            yield movie, hole, subs
+def read_zmws(path: str, is_bam: bool = False, kinetics: bool = False):
+    """Yield (movie, hole, [subreads]) per ZMW, as the CLI's step 0 sees them;
+    with kinetics also the ipd and pw codes per subread (None, None where any
+    subread of the ZMW lacks them): (movie, hole, [subreads], ipd, pw)."""
+    for rec in read_calls(path, is_bam, kinetics):
+        if rec[0] >= 0:
+            yield rec[1:]
 
 
 class SynthBatch:
@@ -422,6 +506,14 @@ class Engine:
                     raise ValueError("Prepared.rev needs one flag per segment")
                 keep.append(rev)
                 arr[i].seg_rev = rev.ctypes.data_as(C.POINTER(C.c_uint8))
+            ipd, pw = getattr(z, "ipd", None), getattr(z, "pw", None)
+            if ipd is not None and pw is not None:
+                if len(ipd) != len(z.seqs) or len(pw) != len(z.seqs):
+                    raise ValueError("Prepared.ipd / .pw need one code per byte of seqs")
+                bi, bp = np.frombuffer(bytes(ipd), np.uint8), np.frombuffer(bytes(pw), np.uint8)
+                keep += [bi, bp]
+                arr[i].ipd = bi.ctypes.data_as(C.POINTER(C.c_uint8))
+                arr[i].pw = bp.ctypes.data_as(C.POINTER(C.c_uint8))
         return arr, keep
 
     def stage(self, zmws: list[Prepared], mode: int | None = None) -> None:
@@ -657,6 +749,27 @@ class Engine:
         if not n.value:
             return np.zeros((0, 12), np.uint8)
         return np.frombuffer(C.string_at(p, n.value * 12), dtype=np.uint8).reshape(n.value, 12).copy()
+
+    def set_kinetics(self, on: bool = True) -> None:
+        """The per-base consensus kinetics for the following stage / run /
+        submit calls (ccsx_gpu_set_kinetics): eight bytes per CCS base (SPEC.md
+        §13) from Prepared.ipd / .pw, read with kinetics()."""
+        if self._L.ccsx_gpu_set_kinetics(self._ctx, 1 if on else 0) != 0:
+            self._err("ccsx_gpu_set_kinetics")
+
+    def kinetics(self, i: int, slot: int = -1) -> np.ndarray:
+        """The kinetics of ZMW i, uint8 [len, 8]: per CCS base the forward
+        reads' code of the mean ipd, code of the mean pw and min(reads, 255),
+        then the reverse reads', then two zero bytes: of the last run() /
+        fetch() (slot -1) or of the batch collected from `slot`; raises if that
+        batch ran with kinetics off or the ZMW failed."""
+        p = C.c_void_p()
+        n = C.c_uint32(0)
+        if self._L.ccsx_gpu_kinetics(self._ctx, slot, i, C.byref(p), C.byref(n)) != 0:
+            self._err("ccsx_gpu_kinetics")
+        if not n.value:
+            return np.zeros((0, 8), np.uint8)
+        return np.frombuffer(C.string_at(p, n.value * 8), dtype=np.uint8).reshape(n.value, 8).copy()
 
     def set_fault(self, i: int) -> None:
         """Test hook (ccsx_gpu_set_fault): the next run() / submit() reports ZMW

@@ -44,7 +44,11 @@ typedef struct {
     const uint32_t *seg_len;  /* nseg lengths */
     uint32_t nseg;
     const uint8_t *seg_rev;   /* nseg strand flags (1: ccs_prepare marked the segment reverse), or NULL = all
-                               * forward; read only with ccsx_gpu_set_pileup on */
+                               * forward; read only with ccsx_gpu_set_pileup or ccsx_gpu_set_kinetics on */
+    const uint8_t *ipd;       /* the 8-bit inter-pulse duration code of every base, parallel to seqs and in the
+                               * orientation the segments are pushed in (SPEC.md section 13), or NULL = none;
+                               * read only with ccsx_gpu_set_kinetics on */
+    const uint8_t *pw;        /* the pulse width codes, likewise (NULL in either: the ZMW has no kinetics) */
 } ccsx_zmw_in;
 
 typedef struct {
@@ -224,6 +228,40 @@ typedef struct {
 } ccsx_pileup;
 int ccsx_gpu_set_pileup(ccsx_ctx *ctx, int on);
 int ccsx_gpu_pileup(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_pileup **p, uint32_t *len);
+/* Per-base consensus kinetics (SPEC.md section 13), off by default: per CCS
+ * base and strand (ccsx_zmw_in::seg_rev; NULL = all forward) the mean
+ * inter-pulse duration and pulse width of the pushed bases that carry the
+ * consensus base in its column, from the per-base codes ccsx_zmw_in::ipd / pw.
+ * on != 0: the following ccsx_gpu_stage* / ccsx_gpu_run / ccsx_gpu_submit calls
+ * give every ZMW one 8-byte record per byte of its output slab, device and
+ * pinned host -- per strand the 8-bit codes of the two means (ccsx_kin_code,
+ * ccsx_host.h) and the number of those bases saturating at 255 -- written once
+ * per launch by the kernel's emission and copied back with the CCS; the two
+ * code planes of the pushed bases (segment by segment in push order) and a
+ * strand byte per segment are staged beside the subreads.  With kinetics on,
+ * ccsx_gpu_zmw_bytes, the batch size ccsx_gpu_submit checks against
+ * ccsx_gpu_slot_bytes and ccsx_gpu_staged_bytes include exactly 8 x the ZMW's
+ * output slab + 2 x the sum of seg_len + nseg per ZMW (a caller sizing
+ * ccsx_gpu_reserve_staging adds 8 x the output bytes to its out_bytes); with it
+ * off those values, the kernels launched and the bytes copied are what they are
+ * without this call, and ipd / pw are not read.  Independent of the other four
+ * outputs.  A batch keeps the setting it was staged or submitted with (the
+ * full-capacity re-run inside ccsx_gpu_collect included).  A ZMW with ipd or pw
+ * NULL gets all-zero records.  The bspoa-compatible single-POA mode
+ * (ccsx_bspoa.h) has no kinetics.
+ * ccsx_gpu_kinetics: the *len (= that ZMW's out[i].len) records of ZMW `zmw` of
+ * a batch, record p for CCS base p: slot -1 = the last ccsx_gpu_run or
+ * ccsx_gpu_fetch on this context, 0 / 1 = that slot's last collected
+ * ccsx_gpu_submit batch.  ctx-owned, valid as long as that batch's out[i].ccs.
+ * Returns -1 (ccsx_gpu_error says why) if the batch ran with kinetics off, is
+ * not collected yet, has no ZMW `zmw`, or that ZMW failed (status != 0).
+ * ccsx_kinetics_tags (ccsx_host.h) formats a ZMW's records as SAM tags. */
+typedef struct {
+    uint8_t fwd[3], rev[3];   /* per strand: code of the mean ipd, code of the mean pw, min(reads, 255) */
+    uint8_t zero[2];
+} ccsx_kinetics;
+int ccsx_gpu_set_kinetics(ccsx_ctx *ctx, int on);
+int ccsx_gpu_kinetics(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_kinetics **rec, uint32_t *len);
 /* The same in three steps (one slice, tight capacities, no re-run), so inputs
  * can stay resident in HBM across launches (used by bench.py).
  * ccsx_gpu_launch returns the kernel time measured with HIP events on the
@@ -238,8 +276,9 @@ int ccsx_gpu_launch(ccsx_ctx *ctx, int mode, float *kernel_ms);
 int ccsx_gpu_fetch(ccsx_ctx *ctx, ccsx_zmw_out *out);
 
 /* Device bytes the staged batch occupies (workspace + arenas; the quality
- * plane, the pass records, the base map and the strand pileup with its strand
- * flags when the batch has them). */
+ * plane, the pass records, the base map, the strand pileup with its strand
+ * flags and the kinetics records with their input planes and strand bytes when
+ * the batch has them). */
 uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *ctx);
 
 /* Diagnostics: per-phase shader-clock counters (s_memtime) summed over the
@@ -300,7 +339,8 @@ int ccsx_gpu_set_mem_wait(ccsx_ctx *ctx, uint32_t ms);
  * capacities: workspace, subreads, output slab -- twice with quality on --,
  * tables, 24 bytes per segment with pass statistics on, 4 bytes per pushed
  * base with the base map on, 12 bytes per output slab byte and one per segment
- * with the strand pileup on). */
+ * with the strand pileup on, 8 bytes per output slab byte, 2 per pushed base
+ * and one per segment with kinetics on). */
 uint64_t ccsx_gpu_zmw_bytes(const ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z);
 /* Test hook: bytes per slot for ccsx_gpu_run's slices (0 = by device memory:
  * half of this context's share, ccsx_gpu_set_mem_share), so a small batch is

@@ -32,6 +32,29 @@ uint32_t ccsx_prepare(const char *seqs, const uint32_t *lens, uint32_t n,
 uint32_t ccsx_prepare_apply(char *seqs, const uint32_t *lens, uint32_t n,
                             uint32_t *seg_off, uint32_t *seg_len);
 
+/* ccsx_prepare_apply with the ZMW's kinetics planes (SPEC.md section 13): ipd
+ * and pw hold one code per base parallel to seqs (either may be NULL); over
+ * every reverse segment both are reversed in place, so that base j of the
+ * segment as pushed keeps the values of the subread base it came from.
+ * seg_rev (may be NULL) receives ccsx_prepare's flags. */
+uint32_t ccsx_prepare_apply_kin(char *seqs, uint8_t *ipd, uint8_t *pw, const uint32_t *lens, uint32_t n,
+                                uint32_t *seg_off, uint32_t *seg_len, uint8_t *seg_rev);
+
+/* The 8-bit kinetics codec (SPEC.md section 13): byte b stands for
+ * ((b & 63) << g) + (64 << g) - 64 frames with g = b >> 6 (0 .. 952);
+ * ccsx_kin_code gives the byte whose frames are nearest to min(f, 952), the
+ * lower byte on a tie. */
+uint32_t ccsx_kin_frames(uint8_t code);
+uint8_t ccsx_kin_code(uint32_t frames);
+
+/* The SAM array tags of a ZMW's kinetics records (ccsx_gpu_kinetics; len
+ * records): "fi:B:C,..<TAB>fp:B:C,..<TAB>ri:B:C,..<TAB>rp:B:C,.." -- the
+ * forward strand's ipd and pw codes in CCS order, the reverse strand's with
+ * the last CCS base first.  Returns the length without the NUL, computed even
+ * when cap is too small; at most cap bytes are written (NUL-terminated when
+ * cap > 0; buf may be NULL with cap 0). */
+long ccsx_kinetics_tags(const ccsx_kinetics *rec, uint32_t len, char *buf, size_t cap);
+
 /* The pairwise aligner used by strand_match (main.c:255-290), standing in for
  * bsalign's kmer_striped_seqedit_pairwise(13, ...) (SPEC.md §8).  q/t are
  * 2-bit codes (values >= 4 never match).  Returns aligned columns (aln). */
@@ -112,6 +135,9 @@ typedef struct ccsx_synth_batch ccsx_synth_batch;
 ccsx_synth_batch *ccsx_synth_batch_make(uint64_t seed, const uint64_t *holes, const uint32_t *L,
                                         const uint32_t *passes, uint32_t n, int nthreads);
 const ccsx_zmw_in *ccsx_synth_batch_zmws(const ccsx_synth_batch *b);
+/* Give every ZMW of the batch synthetic kinetics planes (ccsx_zmw_in::ipd / pw:
+ * a code per base from splitmix64 of seed, the ZMW and the base's index). */
+void ccsx_synth_batch_kinetics(ccsx_synth_batch *b, uint64_t seed);
 void ccsx_synth_batch_free(ccsx_synth_batch *b);
 
 #ifdef __cplusplus

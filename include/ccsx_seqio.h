@@ -27,6 +27,15 @@ ccsx_reader *ccsx_reader_open(const char *path, int is_bam);
 int ccsx_reader_next(ccsx_reader *r, const char **movie, const char **hole, const char **seqs,
                      const uint32_t **lens);
 
+/* ccsx_reader_next and, for BAM input, the subreads' kinetics (SPEC.md section
+ * 13): *ipd / *pw = one 8-bit code per base, parallel to *seqs, from the
+ * records' ip / pw aux arrays (B:C as they are, B:S frames encoded with
+ * ccsx_kin_code, ccsx_host.h); both NULL when any subread of the ZMW lacks
+ * either array (an absent tag, a count other than the record's bases, an aux
+ * field running past the record), and for FASTA / FASTQ input. */
+int ccsx_reader_next_kin(ccsx_reader *r, const char **movie, const char **hole, const char **seqs,
+                         const uint32_t **lens, const uint8_t **ipd, const uint8_t **pw);
+
 void ccsx_reader_close(ccsx_reader *r);
 
 #ifdef __cplusplus

@@ -34,7 +34,7 @@ static int side_outputs()
     const std::vector<Z> five = {{{7, 5, 9}, 40, 0}, {{}, 16, 0}, {{4, 0}, 33, 0}, {{11}, 24, kErrOut}, {{3, 3, 3, 2}, 32, 0}};
     const std::vector<Z> one = {five[2]};
     const size_t perm5[5] = {2, 4, 0, 3, 1};
-    const size_t align[kSideCount] = {1, alignof(uint32_t), alignof(uint32_t), alignof(ccsx_pileup)};
+    const size_t align[kSideCount] = {1, alignof(uint32_t), alignof(uint32_t), alignof(ccsx_pileup), alignof(ccsx_kinetics)};
     for (SideMask m = 0; m <= kSideAll; ++m)
         for (const std::vector<Z> *zs : {(const std::vector<Z> *)nullptr, &one, &five}) {
             const size_t nz = zs ? zs->size() : 0;
