@@ -114,10 +114,13 @@ def build_product(verbose: bool = False) -> str:
     khdrs = [os.path.join(CSRC, "ccsx_layout.h")]  # all the kernel includes
     srcs = [
         os.path.join(CSRC, "ccsx_kernel.hip"),  # compiled once per kernel configuration (KCFGS)
+        os.path.join(CSRC, "ccsx_align.hip"),  # the band aligner's kernel, compiled once
         os.path.join(CSRC, "ccsx_gpu.cpp"),
+        os.path.join(CSRC, "ccsx_align.cpp"),
         os.path.join(CSRC, "bspoa_gpu.cpp"),
         os.path.join(CSRC, "host", "prepare.cpp"),
         os.path.join(CSRC, "host", "pairwise.cpp"),
+        os.path.join(CSRC, "host", "prepare_gpu.cpp"),
         os.path.join(CSRC, "host", "seqio.cpp"),
         os.path.join(CSRC, "host", "dispatch.cpp"),
         os.path.join(CSRC, "host", "ingest.cpp"),
@@ -139,6 +142,12 @@ def build_product(verbose: bool = False) -> str:
     # objects take minutes each; host objects seconds)
     objs, jobs = [], []
     for s in srcs:
+        if s.endswith("ccsx_align.hip"):
+            o = os.path.join(OBJ, "ccsx_align.hip.o")
+            objs.append(o)
+            if _stale(o, [s, os.path.join(CSRC, "ccsx_align.h")]):
+                jobs.append([hipcc, "-x", "hip", "--offload-arch=" + ARCH] + common + ["-c", s, "-o", o])
+            continue
         if s.endswith(".hip"):
             for name, defs in KCFGS:
                 o = os.path.join(OBJ, f"ccsx_kernel_{name}.hip.o")

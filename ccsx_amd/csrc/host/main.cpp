@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -189,6 +190,8 @@ int usage()
             "CCSX_KCFG      Force a kernel configuration (0 latency, 1 occupancy, 2 throughput, 3 solo)\n"
             "CCSX_DEV_SHARE Processes sharing each GPU [1] (each context's memory share shrinks)\n"
             "CCSX_MEM_FRAC  Fraction of each GPU's memory its contexts size their slices from [0.85]\n"
+            "CCSX_GPU_STRAND 1: the band alignments of abnormal subreads (ccs_prepare's strand check) run\n"
+            "               batched per chunk on the first GPU instead of on the -j threads [0]\n"
             "\n"
             "Arguments:\n"
             "input          Input file.\n"
@@ -201,7 +204,11 @@ int usage()
 // input blocks (the copy step 0 of the reference makes, main.c:674-685), then
 // ccs_prepare + strand flip (the CPU half of step 1, main.c:520-536, with its
 // -v output)
-void prepare_chunk(Chunk &ch, int nthreads, int verbose, bool kinetics)
+// With an aligner context (CCSX_GPU_STRAND=1) the middle step runs for the
+// whole chunk at once, its band alignments on the device
+// (ccsx_prepare_batch); if that fails the chunk is prepared on the host, with
+// one warning.
+void prepare_chunk(Chunk &ch, int nthreads, int verbose, bool kinetics, ccsx_aln_ctx *aln, bool timing)
 {
     std::vector<Zmw> &zs = ch.zs;
     // each ZMW's bases at its offset in the chunk's arena
@@ -209,73 +216,129 @@ void prepare_chunk(Chunk &ch, int nthreads, int verbose, bool kinetics)
     for (size_t i = 0; i < zs.size(); ++i) at[i + 1] = at[i] + zs[i].ref.total();
     ch.arena = ch.pool->get(at.back());
     std::atomic<size_t> next(0);
-    auto work = [&]() {
-        std::string msg;
-        for (size_t i; (i = next.fetch_add(1)) < zs.size();) {
-            Zmw &z = zs[i];
-            z.movie = std::move(z.ref.movie);
-            z.hole = std::move(z.ref.hole);
-            z.seqs = ch.arena.p + at[i];
-            z.lens.resize(z.ref.recs.size());
-            size_t o = 0;
-            for (size_t k = 0; k < z.ref.recs.size(); ++k) {
-                const ccsx_ingest::Rec &r = z.ref.recs[k];
-                ccsx_ingest::write_bases(r, &z.seqs[o]);
-                z.lens[k] = r.len;
-                o += r.len;
-            }
-            if (kinetics) {
-                // -k: the two code planes beside the bases, where every subread has them
-                bool have = true;
-                for (const ccsx_ingest::Rec &r : z.ref.recs) have = have && r.has_kinetics();
-                if (have) {
-                    z.kin.resize(2 * o + 2);
-                    size_t q = 0;
-                    for (const ccsx_ingest::Rec &r : z.ref.recs) {
-                        ccsx_ingest::write_kinetics(r, z.kin.data() + q, z.kin.data() + o + q);
-                        q += r.len;
-                    }
-                }
-            }
-            const size_t total = o;
-            ccsx_ingest::ZmwRef().recs.swap(z.ref.recs);
-            std::vector<std::shared_ptr<ccsx_ingest::Block>>().swap(z.ref.keep);
-            const uint32_t n = (uint32_t)z.lens.size();
-            z.seg_off.resize(n);
-            z.seg_len.resize(n);
-            z.seg_rev.resize(n);
-            const uint32_t ns = ccsx_prepare(z.seqs, z.lens.data(), n, z.seg_off.data(), z.seg_len.data(),
-                                             z.seg_rev.data());
-            z.seg_off.resize(ns);
-            z.seg_len.resize(ns);
-            z.seg_rev.resize(ns);
-            msg.clear();
-            if (verbose > 1) msg += "poa begin " + z.hole + "\n";
-            for (uint32_t l = 0; l < ns; ++l) {
-                if (z.seg_rev[l]) ccsx_revcomp(&z.seqs[z.seg_off[l]], z.seg_len[l]);
-                if (z.seg_rev[l] && !z.kin.empty()) {
-                    // (ccsx_prepare_apply_kin: the values stay with their bases)
-                    uint8_t *a = z.kin.data() + z.seg_off[l], *b = z.kin.data() + total + z.seg_off[l];
-                    std::reverse(a, a + z.seg_len[l]);
-                    std::reverse(b, b + z.seg_len[l]);
-                }
-                if (verbose) {
-                    // main.c:477-479 / 533-535
-                    char h[160];
-                    snprintf(h, sizeof h, ">%s_%u/%u strand=%d len=%u \n", z.hole.c_str(), l, ns, z.seg_rev[l],
-                             z.seg_len[l]);
-                    msg += h;
-                    msg.append(z.seqs + z.seg_off[l], z.seg_len[l]);
-                    msg += '\n';
-                }
-            }
-            if (!msg.empty()) fwrite(msg.data(), 1, msg.size(), stderr);
+    // step 0: the bases (and kinetics planes) assembled, the push list sized
+    auto assemble = [&](size_t i) {
+        Zmw &z = zs[i];
+        z.movie = std::move(z.ref.movie);
+        z.hole = std::move(z.ref.hole);
+        z.seqs = ch.arena.p + at[i];
+        z.lens.resize(z.ref.recs.size());
+        size_t o = 0;
+        for (size_t k = 0; k < z.ref.recs.size(); ++k) {
+            const ccsx_ingest::Rec &r = z.ref.recs[k];
+            ccsx_ingest::write_bases(r, &z.seqs[o]);
+            z.lens[k] = r.len;
+            o += r.len;
         }
+        if (kinetics) {
+            // -k: the two code planes beside the bases, where every subread has them
+            bool have = true;
+            for (const ccsx_ingest::Rec &r : z.ref.recs) have = have && r.has_kinetics();
+            if (have) {
+                z.kin.resize(2 * o + 2);
+                size_t q = 0;
+                for (const ccsx_ingest::Rec &r : z.ref.recs) {
+                    ccsx_ingest::write_kinetics(r, z.kin.data() + q, z.kin.data() + o + q);
+                    q += r.len;
+                }
+            }
+        }
+        ccsx_ingest::ZmwRef().recs.swap(z.ref.recs);
+        std::vector<std::shared_ptr<ccsx_ingest::Block>>().swap(z.ref.keep);
+        const uint32_t n = (uint32_t)z.lens.size();
+        z.seg_off.resize(n);
+        z.seg_len.resize(n);
+        z.seg_rev.resize(n);
     };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthreads; ++t) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
+    // step 2: the push list of ns segments applied (strand flip, kinetics
+    // reversal, -v output)
+    auto finish = [&](size_t i, uint32_t ns, std::string &msg) {
+        Zmw &z = zs[i];
+        const size_t total = at[i + 1] - at[i];
+        z.seg_off.resize(ns);
+        z.seg_len.resize(ns);
+        z.seg_rev.resize(ns);
+        msg.clear();
+        if (verbose > 1) msg += "poa begin " + z.hole + "\n";
+        for (uint32_t l = 0; l < ns; ++l) {
+            if (z.seg_rev[l]) ccsx_revcomp(&z.seqs[z.seg_off[l]], z.seg_len[l]);
+            if (z.seg_rev[l] && !z.kin.empty()) {
+                // (ccsx_prepare_apply_kin: the values stay with their bases)
+                uint8_t *a = z.kin.data() + z.seg_off[l], *b = z.kin.data() + total + z.seg_off[l];
+                std::reverse(a, a + z.seg_len[l]);
+                std::reverse(b, b + z.seg_len[l]);
+            }
+            if (verbose) {
+                // main.c:477-479 / 533-535
+                char h[160];
+                snprintf(h, sizeof h, ">%s_%u/%u strand=%d len=%u \n", z.hole.c_str(), l, ns, z.seg_rev[l],
+                         z.seg_len[l]);
+                msg += h;
+                msg.append(z.seqs + z.seg_off[l], z.seg_len[l]);
+                msg += '\n';
+            }
+        }
+        if (!msg.empty()) fwrite(msg.data(), 1, msg.size(), stderr);
+    };
+    auto on_threads = [&](const std::function<void()> &work) {
+        std::vector<std::thread> th;
+        for (int t = 1; t < nthreads; ++t) th.emplace_back(work);
+        work();
+        for (auto &t : th) t.join();
+    };
+    // step 1 on the host: ccs_prepare per ZMW
+    auto host_prepare = [&](size_t i) {
+        Zmw &z = zs[i];
+        return ccsx_prepare(z.seqs, z.lens.data(), (uint32_t)z.lens.size(), z.seg_off.data(), z.seg_len.data(),
+                            z.seg_rev.data());
+    };
+    const auto t0 = std::chrono::steady_clock::now();
+    auto since_t0 = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    if (!aln) {
+        on_threads([&]() {
+            std::string msg;
+            for (size_t i; (i = next.fetch_add(1)) < zs.size();) {
+                assemble(i);
+                finish(i, host_prepare(i), msg);
+            }
+        });
+        if (timing) fprintf(stderr, "[ccsx] chunk %zu prepare: %.1f ms on %d threads\n", ch.id, since_t0(), nthreads);
+        return;
+    }
+    on_threads([&]() {
+        for (size_t i; (i = next.fetch_add(1)) < zs.size();) assemble(i);
+    });
+    const size_t nz = zs.size();
+    std::vector<const char *> seqs(nz);
+    std::vector<const uint32_t *> lens(nz);
+    std::vector<uint32_t> n(nz), nseg(nz, 0);
+    std::vector<uint32_t *> so(nz), sl(nz);
+    std::vector<uint8_t *> sr(nz);
+    for (size_t i = 0; i < nz; ++i) {
+        seqs[i] = zs[i].seqs, lens[i] = zs[i].lens.data(), n[i] = (uint32_t)zs[i].lens.size();
+        so[i] = zs[i].seg_off.data(), sl[i] = zs[i].seg_len.data(), sr[i] = zs[i].seg_rev.data();
+    }
+    ccsx_batch_info bi;
+    const bool ok = ccsx_prepare_batch(aln, seqs.data(), lens.data(), n.data(), nz, nthreads, so.data(), sl.data(),
+                                       sr.data(), nseg.data(), &bi) == 0;
+    if (!ok) {
+        static std::atomic<bool> warned(false);
+        if (!warned.exchange(true))
+            fprintf(stderr, "[ccsx] CCSX_GPU_STRAND: the device aligner failed (%s); preparing on the host\n",
+                    ccsx_gpu_aln_error(aln));
+    } else if (timing) {
+        fprintf(stderr,
+                "[ccsx] chunk %zu strand check: %llu rounds, %llu jobs, seed %.1f ms, device %.1f ms (kernels %.1f ms), "
+                "batched prepare %.1f ms, %.1f ms with the assembly\n",
+                ch.id, (unsigned long long)bi.rounds, (unsigned long long)bi.jobs, bi.seed_ms, bi.device_ms, bi.kernel_ms,
+                bi.total_ms, since_t0());
+    }
+    next = 0;
+    on_threads([&]() {
+        std::string msg;
+        for (size_t i; (i = next.fetch_add(1)) < zs.size();) finish(i, ok ? nseg[i] : host_prepare(i), msg);
+    });
+    if (timing) fprintf(stderr, "[ccsx] chunk %zu prepare: %.1f ms on %d threads\n", ch.id, since_t0(), nthreads);
 }
 
 // the batch queue between step 0 and the device workers
@@ -624,6 +687,9 @@ int main(int argc, char **argv)
     uint32_t last_batches_per_ctx = 1;
     if (const char *e = getenv("CCSX_LAST_BATCHES")) last_batches_per_ctx = (uint32_t)std::max(1, std::min(64, atoi(e)));
     const bool timing = getenv("CCSX_TIMING") && atoi(getenv("CCSX_TIMING"));
+    const bool gpu_strand = getenv("CCSX_GPU_STRAND") && atoi(getenv("CCSX_GPU_STRAND"));
+    ccsx_aln_ctx *aln = nullptr;
+    bool aln_tried = false;
     const auto tstart = std::chrono::steady_clock::now();
     auto now_ms = [tstart]() {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tstart).count();
@@ -1082,7 +1148,15 @@ int main(int argc, char **argv)
         std::vector<Zmw> &zs = ch->zs;
         const size_t id = ch->id;
         const double t0 = ch->t_read0, t1 = ch->t_read1;
-        prepare_chunk(*ch, nthreads, verbose, fp_kin != nullptr);
+        if (gpu_strand && !aln_tried) {
+            // CCSX_GPU_STRAND=1: one aligner context on the first device, opened beside the consensus contexts
+            aln_tried = true;
+            if (ccsx_gpu_aln_open(0, 0, &aln) != 0) {
+                aln = nullptr;
+                fprintf(stderr, "[ccsx] CCSX_GPU_STRAND: cannot open the device aligner; preparing on the host\n");
+            }
+        }
+        prepare_chunk(*ch, nthreads, verbose, fp_kin != nullptr, aln, timing);
         // the chunk's bases are in its arena: its input pages go (a mapped
         // file is unmapped behind the reader instead of all at the exit)
         if (input_release) rd->release(ch->input_hi);
@@ -1176,6 +1250,7 @@ int main(int argc, char **argv)
     }
     for (auto &t : workers) t.join();
     for (auto *x : ctx) ccsx_gpu_close(x);
+    ccsx_gpu_aln_close(aln);
     reap.push(nullptr);
     reaper.join();
     if (timing) fprintf(stderr, "[ccsx] output done at %.0f ms, contexts closed at %.0f ms\n", tw, now_ms());

@@ -4,8 +4,10 @@
 // (called at main.c:264), which is un-vendored.  SPEC.md §8 defines it: k=13
 // exact-seed diagonal vote, then a banded local alignment (match +1,
 // mismatch -2, gap -2) around the winning diagonal.  It only decides strand
-// and trimming of abnormal-length subreads on the host; it is not on the GPU
-// hot path.
+// and trimming of abnormal-length subreads.  Its two halves are separate
+// functions: ccsx_pairwise_seed (the vote) and ccsx_pairwise_band (the band
+// and its traceback); the band also runs on the device, batched over a chunk
+// (ccsx_align.hip), and this one is what it must equal.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -32,12 +34,11 @@ inline uint64_t splitmix64(uint64_t &s)
 
 extern "C" {
 
-ccsx_pairaln ccsx_pairwise(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen)
+// step 1 of SPEC.md §8: the k-mer diagonal vote (diagonal d = tpos - qpos,
+// binned by kBin)
+int ccsx_pairwise_seed(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t *d0_out)
 {
-    ccsx_pairaln r;
-    memset(&r, 0, sizeof r);
-    if (qlen < (uint32_t)kK || tlen < (uint32_t)kK) return r;
-    // 1. k-mer diagonal vote (diagonal d = tpos - qpos, binned by kBin)
+    if (qlen < (uint32_t)kK || tlen < (uint32_t)kK) return 0;
     const uint32_t mask = (1u << (2 * kK)) - 1;
     std::unordered_map<uint32_t, std::vector<uint32_t>> idx;
     idx.reserve(tlen);
@@ -67,13 +68,23 @@ ccsx_pairaln ccsx_pairwise(const uint8_t *q, uint32_t qlen, const uint8_t *t, ui
             votes[d >= 0 ? d / kBin : -((-d + kBin - 1) / kBin)]++;
         }
     }
-    if (votes.empty()) return r;
+    if (votes.empty()) return 0;
     int64_t best_bin = 0;
     uint32_t best_votes = 0;
     for (auto &kv : votes)
         if (kv.second > best_votes || (kv.second == best_votes && kv.first < best_bin))
             best_bin = kv.first, best_votes = kv.second;
-    const int64_t d0 = best_bin * kBin + kBin / 2;
+    *d0_out = (int32_t)(best_bin * kBin + kBin / 2);
+    return 1;
+}
+
+// steps 2 and 3 of SPEC.md §8 (the cell-exact statement the GPU aligner,
+// ccsx_align.hip, reproduces field for field)
+ccsx_pairaln ccsx_pairwise_band(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t d0_in)
+{
+    ccsx_pairaln r;
+    memset(&r, 0, sizeof r);
+    const int64_t d0 = d0_in;
     // 2. banded local alignment over diagonals [d0 - kHalfBand, d0 + kHalfBand]
     const int BW = 2 * kHalfBand + 1;
     std::vector<int32_t> Hprev(BW + 2, 0), Hcur(BW + 2, 0);
@@ -129,6 +140,17 @@ ccsx_pairaln ccsx_pairwise(const uint8_t *q, uint32_t qlen, const uint8_t *t, ui
     }
     r.aln = r.mat + r.mis + r.ins + r.del;
     return r;
+}
+
+ccsx_pairaln ccsx_pairwise(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen)
+{
+    int32_t d0;
+    if (!ccsx_pairwise_seed(q, qlen, t, tlen, &d0)) {
+        ccsx_pairaln r;
+        memset(&r, 0, sizeof r);
+        return r;
+    }
+    return ccsx_pairwise_band(q, qlen, t, tlen, d0);
 }
 
 uint64_t ccsx_synth_zmw(uint64_t seed, uint64_t hole, uint32_t L, uint32_t passes, char *out, uint32_t *lens,

@@ -32,13 +32,17 @@ EXPORTS = {
                    "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
                    "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats",
                    "ccsx_gpu_set_base_map", "ccsx_gpu_base_map", "ccsx_gpu_set_pileup", "ccsx_gpu_pileup",
-                   "ccsx_gpu_set_kinetics", "ccsx_gpu_kinetics"],
+                   "ccsx_gpu_set_kinetics", "ccsx_gpu_kinetics",
+                   "ccsx_gpu_aln_open", "ccsx_gpu_aln_close", "ccsx_gpu_aln_error", "ccsx_gpu_band_align",
+                   "ccsx_gpu_aln_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
                     "ccsx_map_cigar", "ccsx_pileup_call",
                     "ccsx_prepare_apply_kin", "ccsx_kin_frames", "ccsx_kin_code", "ccsx_kinetics_tags",
                     "ccsx_synth_batch_kinetics",
+                    "ccsx_pairwise_seed", "ccsx_pairwise_band", "ccsx_prep_begin", "ccsx_prep_pending",
+                    "ccsx_prep_answer", "ccsx_prep_unused", "ccsx_prep_end", "ccsx_prepare_batch",
                     "ccsx_synth_batch_make", "ccsx_synth_batch_zmws", "ccsx_synth_batch_free"],
     "ccsx_seqio.h": ["ccsx_reader_open", "ccsx_reader_next", "ccsx_reader_next_kin", "ccsx_reader_close"],
 }
@@ -56,6 +60,19 @@ class ZmwOut(C.Structure):
 
 class PairAln(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("qb", "qe", "tb", "te", "mat", "mis", "ins", "del_", "aln", "score")]
+
+
+class Pair(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("qlen", C.c_uint32), ("t", C.c_void_p), ("tlen", C.c_uint32)]
+
+
+class BandJob(C.Structure):
+    _fields_ = [("q", C.c_char_p), ("t", C.c_char_p), ("qlen", C.c_uint32), ("tlen", C.c_uint32), ("d0", C.c_int32)]
+
+
+class BatchInfo(C.Structure):
+    _fields_ = [("rounds", C.c_uint64), ("jobs", C.c_uint64), ("seed_ms", C.c_double), ("device_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 _lib = None
@@ -160,6 +177,33 @@ def lib() -> C.CDLL:
         L.ccsx_prepare_apply.restype = C.c_uint32
         L.ccsx_pairwise.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32]
         L.ccsx_pairwise.restype = PairAln
+        if hasattr(L, "ccsx_gpu_band_align"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_pairwise_seed.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32)]
+            L.ccsx_pairwise_band.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int32]
+            L.ccsx_pairwise_band.restype = PairAln
+            L.ccsx_prep_begin.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32]
+            L.ccsx_prep_begin.restype = C.c_void_p
+            L.ccsx_prep_pending.argtypes = [C.c_void_p, C.POINTER(Pair)]
+            L.ccsx_prep_pending.restype = C.c_uint32
+            L.ccsx_prep_answer.argtypes = [C.c_void_p, C.POINTER(PairAln)]
+            L.ccsx_prep_answer.restype = None
+            L.ccsx_prep_unused.argtypes = [C.c_void_p]
+            L.ccsx_prep_unused.restype = C.c_uint32
+            L.ccsx_prep_end.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+            L.ccsx_prep_end.restype = C.c_uint32
+            L.ccsx_gpu_aln_open.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.ccsx_gpu_aln_close.argtypes = [C.c_void_p]
+            L.ccsx_gpu_aln_close.restype = None
+            L.ccsx_gpu_aln_error.argtypes = [C.c_void_p]
+            L.ccsx_gpu_aln_error.restype = C.c_char_p
+            L.ccsx_gpu_band_align.argtypes = [C.c_void_p, C.POINTER(BandJob), C.c_size_t, C.POINTER(PairAln),
+                                              C.POINTER(C.c_float)]
+            L.ccsx_gpu_aln_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
+            L.ccsx_prepare_batch.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_uint32)),
+                                             C.POINTER(C.c_uint32), C.c_size_t, C.c_int,
+                                             C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
+                                             C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32),
+                                             C.POINTER(BatchInfo)]
         L.ccsx_synth_zmw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p,
                                      C.POINTER(C.c_uint32), C.c_char_p]
         L.ccsx_synth_zmw.restype = C.c_uint64
@@ -297,6 +341,67 @@ def partition(costs, nparts: int, min_batch: int):
 def pairwise(q: bytes, t: bytes) -> dict:
     r = lib().ccsx_pairwise(q, len(q), t, len(t))
     return {n if n != "del_" else "del": getattr(r, n) for n, _ in PairAln._fields_}
+
+
+def _aln_dict(r) -> dict:
+    return {n if n != "del_" else "del": getattr(r, n) for n, _ in PairAln._fields_}
+
+
+def pairwise_seed(q: bytes, t: bytes):
+    """ccsx_pairwise_seed: the 13-mer diagonal vote of SPEC.md §8; the winning
+    diagonal d0, or None when either is shorter than 13 or nothing votes."""
+    d0 = C.c_int32(0)
+    return int(d0.value) if lib().ccsx_pairwise_seed(q, len(q), t, len(t), C.byref(d0)) else None
+
+
+def pairwise_band(q: bytes, t: bytes, d0: int) -> dict:
+    """ccsx_pairwise_band: the banded local alignment around diagonal d0 and
+    its traceback (SPEC.md §8 steps 2-3), on the host."""
+    return _aln_dict(lib().ccsx_pairwise_band(q, len(q), t, len(t), d0))
+
+
+class Prep:
+    """The resumable ccs_prepare of one ZMW (ccsx_prep_*): pending() gives the
+    open request as [(q, t), (q, t)] of 2-bit code bytes or None when the walk
+    has finished, answer() takes the two alignments (dicts as pairwise()
+    returns), end() returns the push list (offs, lens, reverse flags)."""
+
+    def __init__(self, subreads: list[bytes]):
+        self._L = lib()
+        self._seqs = C.create_string_buffer(b"".join(subreads), sum(len(s) for s in subreads) + 1)
+        self._lens = _u32([len(s) for s in subreads])
+        self._n = len(subreads)
+        self._p = self._L.ccsx_prep_begin(self._seqs, _p32(self._lens), self._n)
+
+    def pending(self):
+        w = (Pair * 2)()
+        if not self._L.ccsx_prep_pending(self._p, w):
+            return None
+        return [(C.string_at(x.q, x.qlen), C.string_at(x.t, x.tlen)) for x in w]
+
+    def answer(self, res) -> None:
+        r = (PairAln * 2)()
+        for k in range(2):
+            for n, _ in PairAln._fields_:
+                setattr(r[k], n, res[k]["del" if n == "del_" else n])
+        self._L.ccsx_prep_answer(self._p, r)
+
+    def unused(self) -> int:
+        return int(self._L.ccsx_prep_unused(self._p))
+
+    def end(self):
+        n = max(self._n, 1)
+        so, sl, rv = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        ns = self._L.ccsx_prep_end(self._p, _p32(so), _p32(sl), rv.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._p = None
+        return so[:ns].copy(), sl[:ns].copy(), rv[:ns].copy()
+
+    def __del__(self):
+        try:
+            if self._p:
+                self._L.ccsx_prep_end(self._p, None, None, None)
+        except Exception:
+            pass
 
 
 def qual_phred(match: int, cov: int) -> int:
@@ -461,6 +566,89 @@ def device_count() -> int:
 
 class GpuError(RuntimeError):
     pass
+
+
+class Aligner:
+    """A band aligner context on one HIP device (ccsx_gpu_aln_*): SPEC.md §8's
+    banded alignment of many pairs per launch; max_bytes = the most device
+    memory its arena takes (0: the library's default)."""
+
+    def __init__(self, device: int = 0, max_bytes: int = 0):
+        self._L = lib()
+        self._ctx = C.c_void_p()
+        if self._L.ccsx_gpu_aln_open(device, max_bytes, C.byref(self._ctx)) != 0:
+            raise GpuError(f"cannot open an aligner on HIP device {device}")
+        self.kernel_ms = 0.0
+
+    def close(self):
+        if self._ctx:
+            self._L.ccsx_gpu_aln_close(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what: str):
+        raise GpuError(f"{what}: {self._L.ccsx_gpu_aln_error(self._ctx).decode()}")
+
+    def band_align(self, jobs) -> list:
+        """ccsx_gpu_band_align on jobs = [(q, t, d0)] (2-bit code bytes): one
+        dict per job, as pairwise_band returns; kernel_ms = the kernels' time."""
+        n = len(jobs)
+        arr = (BandJob * max(n, 1))()
+        for i, (q, t, d0) in enumerate(jobs):
+            arr[i].q, arr[i].t, arr[i].qlen, arr[i].tlen, arr[i].d0 = q, t, len(q), len(t), d0
+        out = (PairAln * max(n, 1))()
+        ms = C.c_float(0)
+        if self._L.ccsx_gpu_band_align(self._ctx, arr, n, out, C.byref(ms)) != 0:
+            self._err("ccsx_gpu_band_align")
+        self.kernel_ms = float(ms.value)
+        return [_aln_dict(out[i]) for i in range(n)]
+
+    def pairwise(self, pairs) -> list:
+        """ccsx_pairwise of pairs = [(q, t)] with the seed on the host and the
+        band on the device (a pair without a seed: the all-zero result)."""
+        d0 = [pairwise_seed(q, t) for q, t in pairs]
+        got = iter(self.band_align([(q, t, d) for (q, t), d in zip(pairs, d0) if d is not None]))
+        zero = {n if n != "del_" else "del": 0 for n, _ in PairAln._fields_}
+        return [next(got) if d is not None else dict(zero) for d in d0]
+
+    def prepare_segments(self, zmws, nthreads: int = 4) -> list:
+        """ccsx_prepare_batch: per ZMW (a list of subread bytes) its push list
+        (offs, lens, reverse flags), equal to prepare_segments'; info = the
+        call's rounds, jobs and times."""
+        nz = len(zmws)
+        seqs = [b"".join(z) for z in zmws]
+        lens = [_u32([len(s) for s in z]) for z in zmws]
+        cap = [max(len(z), 1) for z in zmws]
+        so = [np.zeros(c, dtype=np.uint32) for c in cap]
+        sl = [np.zeros(c, dtype=np.uint32) for c in cap]
+        rv = [np.zeros(c, dtype=np.uint8) for c in cap]
+        m = max(nz, 1)
+        a_seq = (C.c_char_p * m)(*seqs)
+        a_len = (C.POINTER(C.c_uint32) * m)(*[_p32(x) for x in lens])
+        a_n = _u32([len(z) for z in zmws])
+        a_so = (C.POINTER(C.c_uint32) * m)(*[_p32(x) for x in so])
+        a_sl = (C.POINTER(C.c_uint32) * m)(*[_p32(x) for x in sl])
+        a_rv = (C.POINTER(C.c_uint8) * m)(*[x.ctypes.data_as(C.POINTER(C.c_uint8)) for x in rv])
+        nseg = np.zeros(m, dtype=np.uint32)
+        info = BatchInfo()
+        if self._L.ccsx_prepare_batch(self._ctx, a_seq, a_len, _p32(a_n), nz, nthreads, a_so, a_sl, a_rv, _p32(nseg),
+                                      C.byref(info)) != 0:
+            self._err("ccsx_prepare_batch")
+        self.info = {n: getattr(info, n) for n, _ in BatchInfo._fields_}
+        return [(so[i][:nseg[i]].copy(), sl[i][:nseg[i]].copy(), rv[i][:nseg[i]].copy()) for i in range(nz)]
+
+    def stats(self) -> dict:
+        """ccsx_gpu_aln_stats: jobs, slices launched, jobs run on the host,
+        rounds and second pairs not consulted (the last two by prepare_segments)."""
+        st = (C.c_uint64 * 5)()
+        if self._L.ccsx_gpu_aln_stats(self._ctx, st, 5) != 0:
+            self._err("ccsx_gpu_aln_stats")
+        return dict(zip(("jobs", "slices", "host_jobs", "rounds", "discarded"), (int(x) for x in st)))
 
 
 class Engine:

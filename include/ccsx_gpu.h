@@ -362,6 +362,46 @@ int ccsx_gpu_profile(ccsx_ctx *ctx, uint64_t *sums, uint32_t nslots);
  * out holds nzmw * nslots values. */
 int ccsx_gpu_profile_zmw(ccsx_ctx *ctx, uint64_t *out, uint32_t nzmw, uint32_t nslots);
 
+/* The band aligner (SPEC.md §8 steps 2-3 on the device, ccsx_align.hip): the
+ * banded local alignment ccs_prepare's strand_match needs for abnormal
+ * subreads, for many pairs per launch.  Every result equals
+ * ccsx_pairwise_band (include/ccsx_host.h) field for field.
+ *
+ * ccsx_pairaln: an alignment of q[qb, qe) to t[tb, te): matches, mismatches,
+ * query bases not in the target (ins), target bases not in the query (del),
+ * aligned columns (their sum) and score (+1 / -2 / -2); all zero = none.
+ *
+ * An aligner context is separate from the consensus contexts: its own stream
+ * and its own device arena of at most max_bytes, allocated at the first job
+ * and grown as slices need; it takes nothing out of a ccsx_ctx's share (the
+ * host program sizes those from CCSX_MEM_FRAC = 0.85 of the device and leaves
+ * the rest free).  max_bytes 0 = 4 GiB: about 1,000 pairs of 15 kb per slice
+ * (a query base costs 256 bytes of traceback records), and a small part of
+ * the 15 % the consensus contexts leave free on a 288 GB device.  The calls on
+ * one context are serialised, so several host threads may share it.
+ * ccsx_gpu_band_align: n jobs (2-bit codes, values >= 4 never match; the band
+ * is the diagonals [d0 - 256, d0 + 256]), cut into slices that fit the arena;
+ * a job whose records alone exceed the arena, or whose lengths or |d0| reach
+ * 2^30, runs ccsx_pairwise_band on the host with the same result.  kernel_ms
+ * (may be NULL) receives the kernels' time by HIP events.  Returns 0 or -1.
+ * ccsx_gpu_aln_stats: counters so far, the first min(n, 5) of: [0] jobs,
+ * [1] slices launched, [2] jobs run on the host, [3] rounds and [4] second
+ * pairs computed but not consulted (both counted by ccsx_prepare_batch). */
+typedef struct {
+    int32_t qb, qe, tb, te, mat, mis, ins, del, aln, score;
+} ccsx_pairaln;
+typedef struct ccsx_aln_ctx ccsx_aln_ctx;
+typedef struct {
+    const uint8_t *q, *t;
+    uint32_t qlen, tlen;
+    int32_t d0;
+} ccsx_band_job;
+int ccsx_gpu_aln_open(int device, uint64_t max_bytes, ccsx_aln_ctx **ctx);
+void ccsx_gpu_aln_close(ccsx_aln_ctx *ctx);
+const char *ccsx_gpu_aln_error(const ccsx_aln_ctx *ctx);
+int ccsx_gpu_band_align(ccsx_aln_ctx *ctx, const ccsx_band_job *jobs, size_t n, ccsx_pairaln *out, float *kernel_ms);
+int ccsx_gpu_aln_stats(const ccsx_aln_ctx *ctx, uint64_t *stats, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

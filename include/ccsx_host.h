@@ -12,7 +12,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "ccsx_gpu.h" /* ccsx_zmw_in */
+#include "ccsx_gpu.h" /* ccsx_zmw_in, ccsx_pairaln, ccsx_aln_ctx */
 
 #ifdef __cplusplus
 extern "C" {
@@ -57,11 +57,68 @@ long ccsx_kinetics_tags(const ccsx_kinetics *rec, uint32_t len, char *buf, size_
 
 /* The pairwise aligner used by strand_match (main.c:255-290), standing in for
  * bsalign's kmer_striped_seqedit_pairwise(13, ...) (SPEC.md §8).  q/t are
- * 2-bit codes (values >= 4 never match).  Returns aligned columns (aln). */
-typedef struct {
-    int32_t qb, qe, tb, te, mat, mis, ins, del, aln, score;
-} ccsx_pairaln;
+ * 2-bit codes (values >= 4 never match).  Returns aligned columns (aln);
+ * ccsx_pairaln is defined in ccsx_gpu.h, beside the device's band aligner. */
 ccsx_pairaln ccsx_pairwise(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen);
+
+/* ccsx_pairwise's two halves (SPEC.md §8), so that the band can run elsewhere
+ * (ccsx_gpu_band_align, include/ccsx_gpu.h).  ccsx_pairwise_seed: the 13-mer
+ * diagonal vote; returns 1 and writes the winning diagonal d0, or 0 when
+ * either length is below 13 or no k-mer votes (ccsx_pairwise then gives the
+ * all-zero result).  ccsx_pairwise_band: the banded local alignment over the
+ * diagonals [d0 - 256, d0 + 256] and its traceback, for any d0 and any
+ * lengths.  ccsx_pairwise is their composition. */
+int ccsx_pairwise_seed(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t *d0);
+ccsx_pairaln ccsx_pairwise_band(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t d0);
+
+/* ccsx_prepare as a resumable walk, for a caller that answers the alignments
+ * of many ZMWs at once (ccsx_prepare_batch).  ccsx_prep_begin starts the walk
+ * of one ZMW (seqs and lens must stay valid until ccsx_prep_end) and runs it
+ * to its first request.  ccsx_prep_pending copies the open request into want
+ * and returns its number of pairs (2), or 0 when the walk has finished.  A
+ * request holds both alignments of one decision: for a subread the forward and
+ * the reverse template, in get_template_grp the head and the tail check; the
+ * second answer is consulted only where strand_match's test, which stays
+ * here, refuses the first.  The pairs are 2-bit codes owned by the walk, valid
+ * until the next ccsx_prep_answer.  ccsx_prep_answer takes the two results
+ * (ccsx_pairwise of each pair, or anything equal to it) and runs on to the
+ * next request.  ccsx_prep_unused: the second answers not consulted so far.
+ * ccsx_prep_end writes the push list as ccsx_prepare does, returns its length
+ * and frees the walk; while a request is pending it writes nothing, returns 0
+ * and frees the walk all the same (the arrays may then be NULL).
+ * ccsx_prepare is this loop with ccsx_pairwise as the answerer. */
+typedef struct {
+    const uint8_t *q;
+    uint32_t qlen;
+    const uint8_t *t;
+    uint32_t tlen;
+} ccsx_pair;
+typedef struct ccsx_prep ccsx_prep;
+ccsx_prep *ccsx_prep_begin(const char *seqs, const uint32_t *lens, uint32_t n);
+uint32_t ccsx_prep_pending(ccsx_prep *p, ccsx_pair want[2]);
+void ccsx_prep_answer(ccsx_prep *p, const ccsx_pairaln res[2]);
+uint32_t ccsx_prep_unused(const ccsx_prep *p);
+uint32_t ccsx_prep_end(ccsx_prep *p, uint32_t *seg_off, uint32_t *seg_len, uint8_t *seg_rev);
+
+/* ccsx_prepare over nz ZMWs with the band alignments of each round run as one
+ * ccsx_gpu_band_align (host/prepare_gpu.cpp): on nthreads threads every walk
+ * is begun; per round every wanted pair is seeded on the threads
+ * (ccsx_pairwise_seed; a pair without a seed gets the all-zero result and no
+ * job), one ccsx_gpu_band_align runs all the jobs, and every walk is answered;
+ * until no walk is pending.  ZMW i is seqs[i] / lens[i] / n[i]; its push list
+ * goes to seg_off[i] / seg_len[i] / seg_rev[i] (room for n[i] entries each)
+ * and its length to nseg[i], all equal to ccsx_prepare's.  info (may be NULL)
+ * receives the rounds, the jobs, and the milliseconds spent seeding, in
+ * ccsx_gpu_band_align, in its kernels, and in all.  Returns 0, or -1 when the
+ * aligner failed (nothing written is valid then; the context's error says
+ * why). */
+typedef struct {
+    uint64_t rounds, jobs;
+    double seed_ms, device_ms, kernel_ms, total_ms;
+} ccsx_batch_info;
+int ccsx_prepare_batch(ccsx_aln_ctx *aln, const char *const *seqs, const uint32_t *const *lens, const uint32_t *n,
+                       size_t nz, int nthreads, uint32_t *const *seg_off, uint32_t *const *seg_len,
+                       uint8_t *const *seg_rev, uint32_t *nseg, ccsx_batch_info *info);
 
 /* Multi-GPU step 1 of the host program (replaces kt_for's dynamic dealing of
  * ZMW indices over threads, kthread.c:24-46).

@@ -1,6 +1,7 @@
 """Write a synthetic subread FASTA: `synth/<hole>/<qs>_<qe>` names,
-single-line uppercase records.  Usage: gen_synth.py OUT.fa NZMW L PASSES [HOLE0]
-(L = 0: per-hole insert length and passes of bench.py's config E)."""
+single-line uppercase records.  Usage: gen_synth.py OUT.fa NZMW L PASSES [HOLE0 [ABNORMAL]]
+(L = 0: per-hole insert length and passes of bench.py's config E; ABNORMAL: the
+fraction of ZMWs that carry an abnormal subread, see abnormal_zmws)."""
 import os
 import struct
 import sys
@@ -29,6 +30,40 @@ def write(path, nzmw, L, passes, hole0=0, seed=20201104, movie="synth", holes=No
     with open(path, "wb") as f:
         for name, s in records(nzmw, L, passes, hole0, seed, movie, holes):
             f.write(b">%s\n%s\n" % (name, s))
+
+
+def write_subreads(path, zmws, hole0=0, movie="synth"):
+    """A FASTA of the given ZMWs (each a list of subread bytes, e.g. the
+    synthetic set with abnormal subreads spliced in), named as above."""
+    with open(path, "wb") as f:
+        for h, subs in enumerate(zmws, hole0):
+            qs = 0
+            for s in subs:
+                f.write(b">%s/%d/%d_%d\n%s\n" % (movie.encode(), h, qs, qs + len(s), s))
+                qs += len(s)
+
+
+def abnormal_zmws(nzmw, L, passes, frac, hole0=0, seed=20201104):
+    """The synthetic set's ZMWs as subread lists, a fraction `frac` of them
+    (every round(1 / frac)-th hole) with one abnormal subread, alternately two
+    passes fused (a missed adapter) and an adapter read-through (a pass
+    followed by most of its reverse complement): what sends ccs_prepare into
+    strand_match's alignments."""
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    every = max(1, round(1 / frac)) if frac > 0 else 0
+    for n, h in enumerate(range(hole0, hole0 + nzmw)):
+        if L:
+            subs, _ = cx.synth_zmw(seed, h, L, passes)
+        else:
+            from bench import CONFIGS, zmw_shape
+            subs, _ = cx.synth_zmw(seed, h, *zmw_shape(CONFIGS["E"], h))
+        if every and n % every == 0:
+            i = len(subs) // 2
+            if (n // every) % 2 == 0:
+                subs[i:i + 2] = [subs[i] + subs[i + 1]]
+            else:
+                subs[i] = subs[i] + subs[i].translate(comp)[::-1][: len(subs[i]) * 3 // 4]
+        yield subs
 
 
 _NT16 = {c: i for i, c in enumerate(b"=ACMGRSVTWYHKDBN")}
@@ -76,4 +111,7 @@ def write_bam(path, recs):
 
 if __name__ == "__main__":
     a = sys.argv
-    write(a[1], int(a[2]), int(a[3]), int(a[4]), int(a[5]) if len(a) > 5 else 0)
+    if len(a) > 6:
+        write_subreads(a[1], abnormal_zmws(int(a[2]), int(a[3]), int(a[4]), float(a[6]), int(a[5])), int(a[5]))
+    else:
+        write(a[1], int(a[2]), int(a[3]), int(a[4]), int(a[5]) if len(a) > 5 else 0)
