@@ -3368,35 +3368,24 @@ __device__ __forceinline__ void pileup_col(const Z &z, uint32_t c, bool v, uint3
 }
 
 // emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag.
-// qual (KArgs::qual, may be null): the quality byte of every base written;
-// PS (the pass-statistics kernels, KArgs::pstat set): the reads' pass records
-// take these columns; BM (the map kernels, KArgs::bmap set; pass records where
-// KArgs::pstat is set too): the reads' bases in these columns get their map
-// entries, from the cursors as the round found them (zi: the ZMW's index);
-// PU (the pileup kernels, KArgs::pile set; pass records and map where their
-// pointers are set): every base written gets its strand pileup record
-// (SPEC.md §12); pc = per strand the bases of the gap-consensus columns emitted
-// since the ZMW's last CCS base (it lives across the rounds, in the caller);
-// KN (the kinetics kernels, KArgs::kin set; pass records, map and pileup where
-// their pointers are set): every base written gets its kinetics record
-// (SPEC.md §13), from the cursors as the round found them
-template <bool PS, bool BM, bool PU, bool KN = false>
+// qual (KArgs::qual, may be null): the quality byte of every base written.
+// SIDE (the side-output kernels): each of KArgs::pstat, bmap, kin and pile that
+// is set gets its output for these columns -- the reads' pass records, their
+// bases' map entries and every written base's kinetics record, from the cursors
+// as the round found them (zi: the ZMW's index), and every written base's
+// strand pileup record; pc = per strand the bases of the gap-consensus columns
+// emitted since the ZMW's last CCS base (it lives across the rounds, in the
+// caller).  Without SIDE none of that code exists.
+template <bool SIDE>
 __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
                                      uint32_t &ol, uint32_t zi, uint32_t (&pc)[2])
 {
-    if constexpr (KN) {
+    if constexpr (SIDE) {
         if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
         if (a.bmap) base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
-        kinetics(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.ksrev + z.d.seg0, a.kipd + a.bmoff[zi],
-                 a.kpw + a.bmoff[zi], a.kin + (size_t)z.d.out_off * kKnBytes);
-    } else if constexpr (PU) {
-        if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
-        if (a.bmap) base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
-    } else if constexpr (BM) {
-        if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
-        base_map(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.bmap + a.bmoff[zi]);
-    } else if constexpr (PS) {
-        pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
+        if (a.kin)
+            kinetics(z, i, n, ol, a.slen + z.d.seg0, a.mode == kShred ? z.pos : nullptr, a.ksrev + z.d.seg0, a.kipd + a.bmoff[zi],
+                     a.kpw + a.bmoff[zi], a.kin + (size_t)z.d.out_off * kKnBytes);
     }
     uint8_t *qual = a.qual ? a.qual + z.d.out_off : nullptr;
     const uint32_t lane = lane_id(), nw = z.d.nw;
@@ -3426,7 +3415,7 @@ __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t 
             if (o < z.d.outcap) out[o] = (uint8_t)"ACGT"[cb];
             if (qual && o < z.d.outcap) qual[o] = column_qual(z, c, n);
         }
-        if (PU || (KN && a.pile)) {
+        if constexpr (SIDE) if (a.pile) {
             uint32_t cnt[2][4], cov[2];
             pileup_col(z, c, c < i, n, a.srev ? a.srev + z.d.seg0 : nullptr, cnt, cov);
             // ins: a gap-consensus column gives its bases, a base column takes
@@ -3495,21 +3484,13 @@ __device__ __forceinline__ void write_msa(Z &z, uint32_t ncols, uint32_t n, uint
 // RD_HBM: the instance for ZMWs whose reads do not fit the LDS read buffer
 // (or whose cursors do not): the read (nibble pairs) and the shredding cursors
 // live in the workspace; every other access is the same code.
-// PS: the instance that also keeps the pass records (SPEC.md §10, KArgs::pstat
-// set).  A kernel of its own rather than a branch on the pointer, so that the
-// kernels every other launch runs are compiled from exactly the code they were
-// before (the branch alone moved the register allocation of the whole kernel:
-// +0.2 % per launch with the feature off).
-// BM: the instance that writes the subread-to-CCS map (SPEC.md §11, KArgs::bmap
-// set), again a kernel of its own; in it the pass records are a branch on
-// KArgs::pstat, so that an object carries one more kernel per instance, not two.
-// PU: the instance that writes the strand pileup (SPEC.md §12, KArgs::pile
-// set), a kernel of its own for the same reason; in it the pass records and the
-// map are branches on their pointers.
-// KN: the instance that writes the consensus kinetics (SPEC.md §13, KArgs::kin
-// set), a kernel of its own again; in it the pass records, the map and the
-// pileup are branches on their pointers.
-template <bool RD_HBM, bool PS, bool BM = false, bool PU = false, bool KN = false>
+// SIDE: the instance that writes the side outputs (SPEC.md §10 to §13), each
+// behind a branch on its KArgs pointer; one kernel serves every selection
+// (DESIGN.md §17).  The plain kernel stays a kernel of its own, so that a launch
+// without side outputs runs exactly the code it ran before there were any: a
+// branch on a pointer alone moved the register allocation of the whole kernel,
+// +0.2 % per launch with the feature off.
+template <bool RD_HBM, bool SIDE>
 __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
 {
     if (blockIdx.x >= a.nzmw) return;
@@ -3563,8 +3544,8 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
     uint32_t *rdoff = P<uint32_t>(z, z.L.rdoff), *rdlen = P<uint32_t>(z, z.L.rdlen);
     uint8_t *out = a.out + z.d.out_off;
     uint32_t ol = 0;
-    uint32_t pc[2] = {0, 0};  // PU: emit's carry of dropped bases, per strand (zero before the ZMW's first POA call)
-    if (BM || PU || KN ? a.pstat != nullptr : PS) {
+    uint32_t pc[2] = {0, 0};  // SIDE: emit's carry of dropped bases, per strand (zero before the ZMW's first POA call)
+    if (SIDE && a.pstat) {
         // the pass records accumulate over the emit calls: a slice launched again starts from zero
         uint32_t *ps = a.pstat + (size_t)z.d.seg0 * kPassWords;
         for (uint32_t x = lane; x < n * kPassWords; x += 64) ps[x] = 0;
@@ -3577,7 +3558,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit<PS, BM, PU, KN>(z, ncols, ncols, n, false, out, a, ol, zi, pc);
+            emit<SIDE>(z, ncols, ncols, n, false, out, a, ol, zi, pc);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3627,7 +3608,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit<PS, BM, PU, KN>(z, i, ncols, n, flag, out, a, ol, zi, pc);
+            emit<SIDE>(z, i, ncols, n, flag, out, a, ol, zi, pc);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {
@@ -3657,31 +3638,10 @@ ccsx_zmw_kernel(KArgs a)
 }
 
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_ps(KArgs a)
+ccsx_zmw_kernel_side(KArgs a)
 {
     extern __shared__ int32_t smem[];
     zmw_body<false, true>(a, smem);
-}
-
-__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_bm(KArgs a)
-{
-    extern __shared__ int32_t smem[];
-    zmw_body<false, false, true>(a, smem);
-}
-
-__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_pu(KArgs a)
-{
-    extern __shared__ int32_t smem[];
-    zmw_body<false, false, false, true>(a, smem);
-}
-
-__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_kn(KArgs a)
-{
-    extern __shared__ int32_t smem[];
-    zmw_body<false, false, false, false, true>(a, smem);
 }
 
 #ifndef CCSX_RING16  // (solo16 takes LDS-instance slices only: ccsx_gpu.cpp stage_slot)
@@ -3693,31 +3653,10 @@ ccsx_zmw_kernel_hbm(KArgs a)
 }
 
 __global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_hbm_ps(KArgs a)
+ccsx_zmw_kernel_hbm_side(KArgs a)
 {
     extern __shared__ int32_t smem[];
     zmw_body<true, true>(a, smem);
-}
-
-__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_hbm_bm(KArgs a)
-{
-    extern __shared__ int32_t smem[];
-    zmw_body<true, false, true>(a, smem);
-}
-
-__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_hbm_pu(KArgs a)
-{
-    extern __shared__ int32_t smem[];
-    zmw_body<true, false, false, true>(a, smem);
-}
-
-__global__ void __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(CCSX_WAVES_PER_EU)))
-ccsx_zmw_kernel_hbm_kn(KArgs a)
-{
-    extern __shared__ int32_t smem[];
-    zmw_body<true, false, false, false, true>(a, smem);
 }
 #endif
 
@@ -3742,26 +3681,15 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
 {
     namespace K = ccsx::CCSX_KCFG;
     if (lds_bytes < (uint32_t)K::kLdsFixed * 4u) return hipErrorInvalidValue;
-    // KArgs::kin selects the kinetics kernels (which branch on KArgs::pile,
-    // KArgs::bmap and KArgs::pstat), else KArgs::pile the pileup kernels (which
-    // branch on KArgs::bmap and KArgs::pstat), else KArgs::bmap the map kernels
-    // (which branch on KArgs::pstat), else KArgs::pstat the pass-statistics kernels
     if ((a->bmap || a->kin) && !a->bmoff) return hipErrorInvalidValue;
     if (a->kin && (!a->kipd || !a->kpw || !a->ksrev)) return hipErrorInvalidValue;
-    void (*k)(ccsx::KArgs) = a->kin    ? &K::ccsx_zmw_kernel_kn
-                             : a->pile ? &K::ccsx_zmw_kernel_pu
-                             : a->bmap ? &K::ccsx_zmw_kernel_bm
-                             : a->pstat ? &K::ccsx_zmw_kernel_ps
-                                        : &K::ccsx_zmw_kernel;
+    // any side output selects the side-output kernels, which branch on each pointer
+    const bool side = a->pstat || a->bmap || a->pile || a->kin;
+    void (*k)(ccsx::KArgs) = side ? &K::ccsx_zmw_kernel_side : &K::ccsx_zmw_kernel;
 #ifdef CCSX_RING16
     if (!a->lds_read_words) return hipErrorInvalidValue;
 #else
-    if (!a->lds_read_words)
-        k = a->kin     ? &K::ccsx_zmw_kernel_hbm_kn
-            : a->pile  ? &K::ccsx_zmw_kernel_hbm_pu
-            : a->bmap  ? &K::ccsx_zmw_kernel_hbm_bm
-            : a->pstat ? &K::ccsx_zmw_kernel_hbm_ps
-                       : &K::ccsx_zmw_kernel_hbm;
+    if (!a->lds_read_words) k = side ? &K::ccsx_zmw_kernel_hbm_side : &K::ccsx_zmw_kernel_hbm;
 #endif
     if (lds_bytes > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
