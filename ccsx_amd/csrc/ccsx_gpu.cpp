@@ -5,7 +5,7 @@
 // launches one workgroup per ZMW and copies the CCS strings back; slices of
 // a large chunk alternate between two slots (streams) so they overlap.
 // The optional per-ZMW outputs beside the CCS (qualities, pass records, map,
-// pileup, kinetics) are described once, in side_out.h: their sizes, their planes in a
+// pileup, kinetics, per-strand consensus) are described once, in side_out.h: their sizes, their planes in a
 // fetched slice, the container a batch's results are gathered into and the
 // accessors' lookup; here they are a mask, loops over it, and their wiring
 // into the kernel's arguments (launch_slot).
@@ -199,7 +199,9 @@ struct Slot {
     // ZMW lie within the 32 that every size counts for a ZMW's tables);
     // kPuBytes per byte of the output slab in d_side[kSidePile], the record of
     // a base at its slab offset, and a strand flag per segment in d_srev
-    // (hsrev: the host copy, the index space of hlen); kKnBytes per byte of
+    // (hsrev: the host copy, the index space of hlen); the by-strand plane
+    // (KArgs::bys: two lengths per ZMW, then four bytes per byte of the output
+    // slab) in d_side[kSideStrand], reading the same d_srev; kKnBytes per byte of
     // the output slab in d_side[kSideKin], its input -- the ipd plane and
     // behind it the pw plane, a byte per pushed base each in the map's index
     // space (hbmoff) -- in d_kin_in (packed in h_kin) and a kinetics strand
@@ -448,7 +450,7 @@ static uint64_t zmw_bytes(const ccsx_zmw_in &zi, bool full, const ccsx_ctx *c, u
     ccsx::zcaps(d, S, lmax, zi.nseg, full, c->tight_rows, shred_win, c->tight_out, c->tight_far);
     ccsx::ZLayout L;
     ccsx::zlayout(L, d);
-    return ccsx::align256(L.total) + hi + d.outcap + ccsx::side_need_of(c->side, d.outcap, zi.nseg, S) +
+    return ccsx::align256(L.total) + hi + d.outcap + ccsx::side_need_of(c->side, 1, d.outcap, zi.nseg, S) +
            uint64_t(zi.nseg) * 8 + sizeof(ccsx::ZmwDesc) + 32;
 }
 
@@ -509,6 +511,8 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     const bool with_map = (side & ccsx::side_bit(ccsx::kSideMap)) != 0;
     const bool with_kin = (side & ccsx::side_bit(ccsx::kSideKin)) != 0;
     const bool with_bmoff = with_map || with_kin;  // the index space of the map and of the kinetics planes
+    // the strand flags of the pileup and of the by-strand output (one device copy serves both)
+    const bool with_srev = (side & (ccsx::side_bit(ccsx::kSidePile) | ccsx::side_bit(ccsx::kSideStrand))) != 0;
     s.hbmoff.resize(with_bmoff ? nz : 0);
     for (size_t i = 0; i < nz; ++i) {
         const ccsx_zmw_in &zi = z[i];
@@ -549,7 +553,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     s.seq_bytes = seq_b, s.ws_bytes = ws_b, s.out_bytes = out_b, s.msa_bytes = msa_b;
     s.bp_words = bp_w;
     s.nseg_total = nseg;
-    s.lay.plan(side, out_b, nseg, nbase);
+    s.lay.plan(side, nz, out_b, nseg, nbase);
     // 2-bit read buffer (ccsx_kernel.hip stage_read); at least one band:
     // every lane reads its window bytes even when the read is shorter.  A
     // slice with a read or a cursor array beyond the LDS budget runs the
@@ -605,7 +609,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         }
     }
     const auto ti = std::chrono::steady_clock::now();
-    const uint64_t need = seq_b + ws_b + out_b + ccsx::side_need_of(side, out_b, nseg, nbase) + msa_b + bp_w * 4 +
+    const uint64_t need = seq_b + ws_b + out_b + ccsx::side_need_of(side, nz, out_b, nseg, nbase) + msa_b + bp_w * 4 +
                           uint64_t(nseg) * 8 + nz * (sizeof(ccsx::ZmwDesc) + 32);
     {
         // a neighbour still holding memory: wait for it (ccsx_gpu_run has
@@ -640,7 +644,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
         HIPCHK(c, s.d_ksrev.reserve(std::max<size_t>(nseg, 1)));
         HIPCHK(c, s.d_kin_in.reserve(std::max<uint64_t>(2 * nbase, 1)));
     }
-    if (s.lay.has(ccsx::kSidePile)) HIPCHK(c, s.d_srev.reserve(nseg));
+    if (with_srev) HIPCHK(c, s.d_srev.reserve(nseg));
     HIPCHK(c, s.d_msa.reserve(msa_b));
     HIPCHK(c, s.d_olen.reserve(nz * 4));
     HIPCHK(c, s.d_ncols.reserve(nz * 4));
@@ -728,7 +732,7 @@ static int stage_slot(ccsx_ctx *c, Slot &s, const ccsx_zmw_in *z, size_t nz, int
     HIPCHK(c, hipMemcpyAsync(s.d_slen.p, s.hlen.data(), size_t(nseg) * 4, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipMemcpyAsync(s.d_desc.p, s.desc.data(), nz * sizeof(ccsx::ZmwDesc), hipMemcpyHostToDevice, s.stream));
     if (with_bmoff && nz) HIPCHK(c, hipMemcpyAsync(s.d_bmoff.p, s.hbmoff.data(), nz * 8, hipMemcpyHostToDevice, s.stream));
-    if (s.lay.has(ccsx::kSidePile)) {
+    if (with_srev) {
         // the strand flags, read only here: a ZMW without them is all forward
         s.hsrev.assign(nseg, 0);
         for (size_t i = 0; i < nz; ++i)
@@ -808,7 +812,8 @@ static int launch_slot(ccsx_ctx *c, Slot &s, int mode)
     a.bmap = L.plane[ccsx::kSideMap] ? s.d_side[ccsx::kSideMap].as<uint32_t>() : nullptr;
     a.bmoff = L.plane[ccsx::kSideMap] || L.plane[ccsx::kSideKin] ? s.d_bmoff.as<uint64_t>() : nullptr;
     a.pile = L.plane[ccsx::kSidePile] ? s.d_side[ccsx::kSidePile].as<uint8_t>() : nullptr;
-    a.srev = L.plane[ccsx::kSidePile] && s.nseg_total ? s.d_srev.as<uint8_t>() : nullptr;
+    a.bys = L.plane[ccsx::kSideStrand] ? s.d_side[ccsx::kSideStrand].as<uint8_t>() : nullptr;
+    a.srev = (a.pile || a.bys) && s.nseg_total ? s.d_srev.as<uint8_t>() : nullptr;
     if (L.plane[ccsx::kSideKin]) {
         a.kin = s.d_side[ccsx::kSideKin].as<uint8_t>();
         a.kipd = s.d_kin_in.as<uint8_t>();
@@ -1549,6 +1554,7 @@ int ccsx_gpu_set_pass_stats(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSid
 int ccsx_gpu_set_base_map(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideMap, on); }
 int ccsx_gpu_set_pileup(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSidePile, on); }
 int ccsx_gpu_set_kinetics(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideKin, on); }
+int ccsx_gpu_set_by_strand(ccsx_ctx *c, int on) { return set_side(c, ccsx::kSideStrand, on); }
 
 // The accessors' common part: output o of ZMW `zmw` of the batch collected from
 // `slot`, or (slot -1) of the last ccsx_gpu_run's gathered results or the slice
@@ -1633,6 +1639,24 @@ int ccsx_gpu_kinetics(ccsx_ctx *c, int slot, size_t zmw, const ccsx_kinetics **r
     return 0;
 }
 
+int ccsx_gpu_by_strand(ccsx_ctx *c, int slot, size_t zmw, int strand, const char **seq, const uint8_t **qual, uint32_t *len)
+{
+    if (!c || !seq || !qual || !len) return -1;
+    *seq = nullptr;
+    *qual = nullptr;
+    *len = 0;
+    if (strand != 0 && strand != 1) {
+        c->err = "strand must be 0 (forward) or 1 (reverse)";
+        return -1;
+    }
+    ccsx::SideRec r;
+    if (side_lookup(c, slot, zmw, ccsx::kSideStrand, r)) return -1;
+    *seq = reinterpret_cast<const char *>(r.sseq[strand]);
+    *qual = r.squal[strand];
+    *len = r.slen[strand];
+    return 0;
+}
+
 int ccsx_gpu_set_prealloc(ccsx_ctx *c, int on)
 {
     if (!c) return -1;
@@ -1683,7 +1707,7 @@ uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *c)
 {
     if (!c) return 0;
     const Slot &s = c->slot[0];
-    return s.seq_bytes + s.ws_bytes + s.out_bytes + ccsx::side_need_of(s.lay.mask, s.out_bytes, s.nseg_total, s.nbase_total) +
+    return s.seq_bytes + s.ws_bytes + s.out_bytes + ccsx::side_need_of(s.lay.mask, s.nz, s.out_bytes, s.nseg_total, s.nbase_total) +
            s.msa_bytes;
 }
 

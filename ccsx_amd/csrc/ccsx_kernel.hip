@@ -3369,16 +3369,19 @@ __device__ __forceinline__ void pileup_col(const Z &z, uint32_t c, bool v, uint3
 
 // emit the consensus of columns [0, i) (main.c:622-638); advance pos if flag.
 // qual (KArgs::qual, may be null): the quality byte of every base written.
-// SIDE (the side-output kernels): each of KArgs::pstat, bmap, kin and pile that
+// SIDE (the side-output kernels): each of KArgs::pstat, bmap, kin, pile and bys that
 // is set gets its output for these columns -- the reads' pass records, their
 // bases' map entries and every written base's kinetics record, from the cursors
 // as the round found them (zi: the ZMW's index), and every written base's
 // strand pileup record; pc = per strand the bases of the gap-consensus columns
 // emitted since the ZMW's last CCS base (it lives across the rounds, in the
-// caller).  Without SIDE none of that code exists.
+// caller).  KArgs::bys: every emitted column in which a strand's reads call a
+// base (SPEC.md §14) gives that strand's consensus the base and its quality;
+// sl = per strand the bases written so far (the caller's, like pc).  Without
+// SIDE none of that code exists.
 template <bool SIDE>
 __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t n, bool flag, uint8_t *out, const KArgs &a,
-                                     uint32_t &ol, uint32_t zi, uint32_t (&pc)[2])
+                                     uint32_t &ol, uint32_t zi, uint32_t (&pc)[2], uint32_t (&sl)[2])
 {
     if constexpr (SIDE) {
         if (a.pstat) pass_stats(z, i, n, ol, a.pstat + (size_t)z.d.seg0 * kPassWords);
@@ -3415,42 +3418,69 @@ __device__ __forceinline__ void emit(Z &z, uint32_t i, uint32_t ncols, uint32_t 
             if (o < z.d.outcap) out[o] = (uint8_t)"ACGT"[cb];
             if (qual && o < z.d.outcap) qual[o] = column_qual(z, c, n);
         }
-        if constexpr (SIDE) if (a.pile) {
+        if constexpr (SIDE) if (a.pile || a.bys) {
+            // (one walk of the column serves both outputs)
             uint32_t cnt[2][4], cov[2];
             pileup_col(z, c, c < i, n, a.srev ? a.srev + z.d.seg0 : nullptr, cnt, cov);
-            // ins: a gap-consensus column gives its bases, a base column takes
-            // those since the base column before it -- the difference of the
-            // inclusive sums at the two lanes, the carry pc before the chunk's
-            // first base column
-            const uint64_t lo = bal & ((1ull << lane) - 1ull);  // the base columns below this lane's
-            const uint32_t prev = lo ? 63u - (uint32_t)__builtin_clzll(lo) : 0u;
-            const uint32_t top = bal ? 63u - (uint32_t)__builtin_clzll(bal) : 0u;  // the chunk's last base column
-            uint32_t rec[2][kPuFields];
+            if (a.pile) {
+                // ins: a gap-consensus column gives its bases, a base column takes
+                // those since the base column before it -- the difference of the
+                // inclusive sums at the two lanes, the carry pc before the chunk's
+                // first base column
+                const uint64_t lo = bal & ((1ull << lane) - 1ull);  // the base columns below this lane's
+                const uint32_t prev = lo ? 63u - (uint32_t)__builtin_clzll(lo) : 0u;
+                const uint32_t top = bal ? 63u - (uint32_t)__builtin_clzll(bal) : 0u;  // the chunk's last base column
+                uint32_t rec[2][kPuFields];
 #pragma unroll
-            for (uint32_t s = 0; s < 2; ++s) {
-                const uint32_t tot = cnt[s][0] + cnt[s][1] + cnt[s][2] + cnt[s][3];
-                const uint32_t sum = wave_incl_add(c < i && cb >= 4 ? tot : 0u);
-                const uint32_t at = (uint32_t)__shfl((int)sum, (int)prev);
-                const uint32_t ins = lo ? sum - at : sum + pc[s];
-                const uint32_t end = (uint32_t)__builtin_amdgcn_readlane((int)sum, 63);
-                const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)sum, (int)uni(top));
-                pc[s] = bal ? end - last : pc[s] + end;
+                for (uint32_t s = 0; s < 2; ++s) {
+                    const uint32_t tot = cnt[s][0] + cnt[s][1] + cnt[s][2] + cnt[s][3];
+                    const uint32_t sum = wave_incl_add(c < i && cb >= 4 ? tot : 0u);
+                    const uint32_t at = (uint32_t)__shfl((int)sum, (int)prev);
+                    const uint32_t ins = lo ? sum - at : sum + pc[s];
+                    const uint32_t end = (uint32_t)__builtin_amdgcn_readlane((int)sum, 63);
+                    const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)sum, (int)uni(top));
+                    pc[s] = bal ? end - last : pc[s] + end;
 #pragma unroll
-                for (uint32_t b = 0; b < 4; ++b) rec[s][b] = sat8(cnt[s][b]);
-                rec[s][kPuGap] = sat8(cov[s] - tot);
-                rec[s][kPuIns] = sat8(ins);
+                    for (uint32_t b = 0; b < 4; ++b) rec[s][b] = sat8(cnt[s][b]);
+                    rec[s][kPuGap] = sat8(cov[s] - tot);
+                    rec[s][kPuIns] = sat8(ins);
+                }
+                const uint32_t o = ol + lanes_below(bal);
+                if (cb < 4 && o < z.d.outcap) {
+                    uint32_t *p = reinterpret_cast<uint32_t *>(a.pile + ((size_t)z.d.out_off + o) * kPuBytes);
+                    p[0] = rec[0][0] | rec[0][1] << 8 | rec[0][2] << 16 | rec[0][3] << 24;
+                    p[1] = rec[0][4] | rec[0][5] << 8 | rec[1][0] << 16 | rec[1][1] << 24;
+                    p[2] = rec[1][2] | rec[1][3] << 8 | rec[1][4] << 16 | rec[1][5] << 24;
+                }
             }
-            const uint32_t o = ol + lanes_below(bal);
-            if (cb < 4 && o < z.d.outcap) {
-                uint32_t *p = reinterpret_cast<uint32_t *>(a.pile + ((size_t)z.d.out_off + o) * kPuBytes);
-                p[0] = rec[0][0] | rec[0][1] << 8 | rec[0][2] << 16 | rec[0][3] << 24;
-                p[1] = rec[0][4] | rec[0][5] << 8 | rec[1][0] << 16 | rec[1][1] << 24;
-                p[2] = rec[1][2] | rec[1][3] << 8 | rec[1][4] << 16 | rec[1][5] << 24;
+            if (a.bys) {
+                // SPEC.md §14: §6's call on each strand's counts; the strand's
+                // bases are packed by its own ballot behind its cursor sl[s].
+                // A lane without an emitted column has cov = 0: no call
+                uint8_t *sp = a.bys + (size_t)a.nzmw * 8 + (size_t)z.d.out_off * 4;
+#pragma unroll
+                for (uint32_t s = 0; s < 2; ++s) {
+                    uint32_t best = 0, bc = cnt[s][0];
+#pragma unroll
+                    for (uint32_t b = 1; b < 4; ++b)
+                        if (cnt[s][b] > bc) best = b, bc = cnt[s][b];
+                    const uint32_t gap = cov[s] - (cnt[s][0] + cnt[s][1] + cnt[s][2] + cnt[s][3]);
+                    const bool has = cov[s] != 0 && bc >= gap;
+                    const uint64_t sb = ballot(has);
+                    const uint32_t o = sl[s] + lanes_below(sb);
+                    if (has && o < z.d.outcap) {
+                        uint8_t *p = sp + (size_t)(2 * s) * z.d.outcap;
+                        p[o] = (uint8_t)"ACGT"[best];
+                        p[z.d.outcap + o] = qual_phred(bc, cov[s]);
+                    }
+                    sl[s] += (uint32_t)__builtin_popcountll(sb);
+                }
             }
         }
         ol += (uint32_t)__builtin_popcountll(bal);
     }
     if (ol > z.d.outcap) z.status = kErrOut;
+    if constexpr (SIDE) if (a.bys && (sl[0] > z.d.outcap || sl[1] > z.d.outcap)) z.status = kErrOut;
     wsync();
 }
 
@@ -3484,7 +3514,7 @@ __device__ __forceinline__ void write_msa(Z &z, uint32_t ncols, uint32_t n, uint
 // RD_HBM: the instance for ZMWs whose reads do not fit the LDS read buffer
 // (or whose cursors do not): the read (nibble pairs) and the shredding cursors
 // live in the workspace; every other access is the same code.
-// SIDE: the instance that writes the side outputs (SPEC.md §10 to §13), each
+// SIDE: the instance that writes the side outputs (SPEC.md §10 to §14), each
 // behind a branch on its KArgs pointer; one kernel serves every selection
 // (DESIGN.md §17).  The plain kernel stays a kernel of its own, so that a launch
 // without side outputs runs exactly the code it ran before there were any: a
@@ -3545,6 +3575,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
     uint8_t *out = a.out + z.d.out_off;
     uint32_t ol = 0;
     uint32_t pc[2] = {0, 0};  // SIDE: emit's carry of dropped bases, per strand (zero before the ZMW's first POA call)
+    uint32_t sl[2] = {0, 0};  // SIDE: emit's cursors of the two strand consensuses (SPEC.md §14), likewise
     if (SIDE && a.pstat) {
         // the pass records accumulate over the emit calls: a slice launched again starts from zero
         uint32_t *ps = a.pstat + (size_t)z.d.seg0 * kPassWords;
@@ -3558,7 +3589,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         wsync();
         const uint32_t ncols = run_poa(z, n, z.seq);
         if (!z.status) {
-            emit<SIDE>(z, ncols, ncols, n, false, out, a, ol, zi, pc);
+            emit<SIDE>(z, ncols, ncols, n, false, out, a, ol, zi, pc, sl);
             if (a.mode == kSinglePoa && !z.status) {
                 if ((uint64_t)ncols * (n + 4) > z.d.msacap) z.status = kErrOut;
                 else write_msa(z, ncols, n, a.msa + z.d.msa_off);
@@ -3608,7 +3639,7 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
                 ++nround;
             }
             const unsigned long long te0 = pstamp();
-            emit<SIDE>(z, i, ncols, n, flag, out, a, ol, zi, pc);
+            emit<SIDE>(z, i, ncols, n, flag, out, a, ol, zi, pc, sl);
             z.pf[kPfShred] += pstamp() - te0;
         }
         if (a.bplog) {
@@ -3621,6 +3652,10 @@ __device__ __forceinline__ void zmw_body(const KArgs &a, int32_t *smem)
         a.out_len[zi] = ol;
         a.status[zi] = z.status;
         a.cells[zi] = z.cells;
+        if constexpr (SIDE) if (a.bys) {
+            uint32_t *ln = reinterpret_cast<uint32_t *>(a.bys) + 2 * (size_t)zi;
+            ln[0] = sl[0], ln[1] = sl[1];
+        }
         if (a.prof) {
             z.pf[kPfTotal] = pstamp() - t_start;
             z.pf[kPfEndRt] = prealtime();
@@ -3684,7 +3719,7 @@ extern "C" hipError_t CCSX_LAUNCH(const ccsx::KArgs *a, uint32_t lds_bytes, hipS
     if ((a->bmap || a->kin) && !a->bmoff) return hipErrorInvalidValue;
     if (a->kin && (!a->kipd || !a->kpw || !a->ksrev)) return hipErrorInvalidValue;
     // any side output selects the side-output kernels, which branch on each pointer
-    const bool side = a->pstat || a->bmap || a->pile || a->kin;
+    const bool side = a->pstat || a->bmap || a->pile || a->kin || a->bys;
     void (*k)(ccsx::KArgs) = side ? &K::ccsx_zmw_kernel_side : &K::ccsx_zmw_kernel;
 #ifdef CCSX_RING16
     if (!a->lds_read_words) return hipErrorInvalidValue;

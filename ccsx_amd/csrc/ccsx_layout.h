@@ -317,11 +317,15 @@ struct KArgs {
     uint32_t *bmap;            // optional: a map word per pushed base (SPEC.md §11); the ZMW's segments back to back at bmoff[zmw]
     const uint64_t *bmoff;     // with bmap: per ZMW, the word offset of its map (the pushed bases of the ZMWs before it)
     uint8_t *pile;             // optional: kPuBytes per CCS byte at (ZmwDesc::out_off + offset) * kPuBytes (SPEC.md §12)
-    const uint8_t *srev;       // optional, read with pile: a strand flag per segment at ZmwDesc::seg0 + k (null: all forward)
+    const uint8_t *srev;       // optional, read with pile and bys: a strand flag per segment at ZmwDesc::seg0 + k (null: all forward)
     uint8_t *kin;              // optional: kKnBytes per CCS byte at (ZmwDesc::out_off + offset) * kKnBytes (SPEC.md §13); needs bmoff
     const uint8_t *kipd;       // with kin: an ipd code per pushed base, the map's index space (bmoff[zmw] + the base's entry)
     const uint8_t *kpw;        // with kin: a pw code per pushed base, likewise
     const uint8_t *ksrev;      // with kin: a kinetics strand byte (kKnRev | kKnNone) per segment at ZmwDesc::seg0 + k
+    // optional: the by-strand plane (SPEC.md §14): the two lengths (forward, reverse) of ZMW i in words 2 i and
+    // 2 i + 1, and behind the nzmw pairs four slabs of ZmwDesc::outcap bytes per ZMW at 8 nzmw + 4 ZmwDesc::out_off:
+    // the forward strand's bases and qualities, then the reverse strand's
+    uint8_t *bys;
 };
 
 // phase counters written when KArgs::prof != nullptr

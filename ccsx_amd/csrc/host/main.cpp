@@ -126,6 +126,7 @@ struct Zmw {
     std::vector<ccsx_pass_stat> pst;  // -r: one record per segment (SPEC.md section 10)
     std::string paf;          // -a: the PAF lines of its segments (SPEC.md section 11)
     std::string sites;        // -s: the lines of its discordant sites (SPEC.md section 12)
+    std::string strands;      // -b: the records of its strand consensuses (SPEC.md section 14)
     std::vector<uint8_t> kin;  // -k: the ipd codes of its bases, then the pw codes, parallel to seqs (empty: a subread lacks them)
     std::string kinline;      // -k: its SAM line (SPEC.md section 13)
     bool kin_arrays = false;  // -k: ... carries the four arrays
@@ -175,6 +176,7 @@ int usage()
             "-r     <file>  Pass report (tab-separated): per subread, its match/mismatch/ins/del counts against the CCS, the CCS stretch it covers, identity \n"
             "-a     <file>  Subread-to-CCS alignments (PAF, cg:Z: with =/X/I/D): per subread, where its bases lie in the CCS by the alignment the CCS was called from \n"
             "-s     <file>  Strand-discordant sites (tab-separated): per CCS position whose forward and reverse subreads call different bases (or base against gap), the two calls and the per-strand A/C/G/T/gap/ins counts \n"
+            "-b     <file>  Per-strand consensus (fasta, fastq with -q): per CCS read the sequence its forward and its reverse subreads support in the alignment the CCS was called from, as <name>/fwd and <name>/rev in the CCS's orientation \n"
             "-k     <file>  Consensus kinetics (unaligned SAM; BAM input only): per CCS read its bases, np/fn/rn and, from the subreads' ip/pw tags, the per-strand mean inter-pulse duration and pulse width per base as fi/fp/ri/rp B:C arrays \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
@@ -556,10 +558,11 @@ int main(int argc, char **argv)
     const char *paf_path = nullptr;     // -a
     const char *site_path = nullptr;    // -s
     const char *kin_path = nullptr;     // -k
+    const char *strand_path = nullptr;  // -b
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -570,6 +573,7 @@ int main(int argc, char **argv)
         case 'a': paf_path = optarg; break;
         case 's': site_path = optarg; break;
         case 'k': kin_path = optarg; break;
+        case 'b': strand_path = optarg; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -633,6 +637,11 @@ int main(int argc, char **argv)
     }
     FILE *fp_kin = kin_path ? fopen(kin_path, "w") : nullptr;
     if (kin_path && !fp_kin) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    FILE *fp_str = strand_path ? fopen(strand_path, "w") : nullptr;
+    if (strand_path && !fp_str) {
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
@@ -741,7 +750,7 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
-        bool qfail = false;  // -q / -r / -a / -s / -k: the batch's qualities, pass records, maps, pileups or kinetics are missing (a context error)
+        bool qfail = false;  // -q / -r / -a / -s / -k / -b: the batch's qualities, pass records, maps, pileups, kinetics or strand consensuses are missing (a context error)
         if (r == 0 || r == -2) {
             // -2: some ZMWs failed on the device, the rest are valid
             uint64_t cells = 0;
@@ -857,6 +866,38 @@ int main(int argc, char **argv)
                     }
                     s += '\n';
                     std::vector<uint8_t>().swap(z.kin);
+                }
+                if (fp_str && !f.out[i].status && f.out[i].len) {
+                    // the forward, then the reverse strand's record, laid out as the main output's
+                    char head[96];
+                    for (int sd = 0; sd < 2 && !qfail; ++sd) {
+                        const char *sq = nullptr;
+                        const uint8_t *q = nullptr;
+                        uint32_t sn = 0;
+                        if (ccsx_gpu_by_strand(ctx[w], f.slot, i, sd, &sq, &q, &sn) != 0) {
+                            qfail = true;
+                            break;
+                        }
+                        if (!sn) continue;
+                        size_t np = 0;
+                        for (uint8_t v : z.seg_rev) np += (v != 0) == (sd != 0);
+                        std::string &s = z.strands;
+                        s += fastq ? '@' : '>';
+                        s += z.movie + "/" + z.hole + (sd ? "/ccs/rev" : "/ccs/fwd");
+                        if (fastq) {
+                            snprintf(head, sizeof head, " np=%zu rq=%.6f", np, ccsx_qual_rq(q, sn));
+                            s += head;
+                        }
+                        s += '\n';
+                        s.append(sq, sn);
+                        s += '\n';
+                        if (fastq) {
+                            s += "+\n";
+                            for (uint32_t k = 0; k < sn; ++k) s += (char)(q[k] + 33);
+                            s += '\n';
+                        }
+                    }
+                    if (qfail) break;
                 }
                 const uint32_t *lg;
                 uint32_t nr = 0;
@@ -1056,6 +1097,7 @@ int main(int argc, char **argv)
             if (fp_paf) ccsx_gpu_set_base_map(ctx[i], 1);
             if (fp_site) ccsx_gpu_set_pileup(ctx[i], 1);
             if (fp_kin) ccsx_gpu_set_kinetics(ctx[i], 1);
+            if (fp_str) ccsx_gpu_set_by_strand(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
@@ -1127,6 +1169,7 @@ int main(int argc, char **argv)
                         }
                     if (fp_paf) fwrite(z.paf.data(), 1, z.paf.size(), fp_paf);
                     if (fp_site) fwrite(z.sites.data(), 1, z.sites.size(), fp_site);
+                    if (fp_str) fwrite(z.strands.data(), 1, z.strands.size(), fp_str);
                     if (fp_kin) {
                         if (!z.kin_arrays) ++nokin;
                         fwrite(z.kinline.data(), 1, z.kinline.size(), fp_kin);
@@ -1216,6 +1259,7 @@ int main(int argc, char **argv)
         if (fp_paf) werr = (ferror(fp_paf) || fclose(fp_paf) != 0) || werr;
         if (fp_site) werr = (ferror(fp_site) || fclose(fp_site) != 0) || werr;
         if (fp_kin) werr = (ferror(fp_kin) || fclose(fp_kin) != 0) || werr;
+        if (fp_str) werr = (ferror(fp_str) || fclose(fp_str) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1261,6 +1305,7 @@ int main(int argc, char **argv)
     if (fp_paf) (void)fclose(fp_paf);
     if (fp_site) (void)fclose(fp_site);
     if (fp_kin) (void)fclose(fp_kin);
+    if (fp_str) (void)fclose(fp_str);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

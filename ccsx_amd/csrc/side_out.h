@@ -1,6 +1,6 @@
 // side_out.h -- the engine's optional per-ZMW outputs beside the CCS (the
 // "side outputs": qualities, pass records, subread-to-CCS map, strand pileup,
-// consensus kinetics; SPEC.md §9-§13), each described once: what it costs, where its plane lies in
+// consensus kinetics, per-strand consensus; SPEC.md §9-§14), each described once: what it costs, where its plane lies in
 // a fetched slice, how a batch's results are gathered and how an accessor finds
 // them.  No HIP here: ccsx_gpu.cpp owns the device side (DESIGN.md §14 lists
 // what a further output has to touch); tools/host_sanitize.cpp drives this file
@@ -15,7 +15,7 @@
 
 namespace ccsx {
 
-enum SideOut : int { kSideQual = 0, kSidePass, kSideMap, kSidePile, kSideKin, kSideCount };
+enum SideOut : int { kSideQual = 0, kSidePass, kSideMap, kSidePile, kSideKin, kSideStrand, kSideCount };
 typedef uint32_t SideMask;  // bit o: output o is on
 constexpr SideMask side_bit(int o) { return SideMask(1) << o; }
 constexpr SideMask kSideAll = side_bit(kSideCount) - 1;
@@ -23,56 +23,64 @@ constexpr SideMask kSideAll = side_bit(kSideCount) - 1;
 static_assert(sizeof(ccsx_pass_stat) == kPassWords * 4, "ccsx_pass_stat is the kernel's record");
 static_assert(sizeof(ccsx_pileup) == kPuBytes, "ccsx_pileup is the kernel's record");
 static_assert(sizeof(ccsx_kinetics) == kKnBytes, "ccsx_kinetics is the kernel's record");
+// the by-strand output's two length words per ZMW (forward, reverse; SPEC.md §14)
+constexpr uint32_t kBysLenBytes = 8;
 
-// One row per output.  Its plane takes per_slab bytes per byte of the output
-// slab + per_seg per segment + per_base per pushed base; flags_per_seg more
-// bytes per segment are an input of its own (the pileup's strand flags, the
-// kinetics' strand bytes), copied back behind the plane; in_per_base more bytes
+// One row per output.  Its plane takes per_zmw bytes per ZMW (the by-strand
+// output's two lengths, at the plane's start) + per_slab bytes per byte of the
+// output slab + per_seg per segment + per_base per pushed base; flags_per_seg
+// more bytes per segment are an input of its own (the strand flags of the
+// pileup and of the by-strand output, the kinetics' strand bytes), copied back
+// behind the plane; in_per_base more bytes
 // per pushed base are an input that stays on the device (the kinetics' two code
 // planes): they count in every device size (side_need_of), not in the fetched
 // slice.
 struct SideInfo {
-    uint32_t per_slab, per_seg, per_base, flags_per_seg, in_per_base;
+    uint32_t per_slab, per_seg, per_base, flags_per_seg, in_per_base, per_zmw;
     bool in_out;         // the plane lies directly behind the CCS plane in the output buffer and is
                          // fetched with it, at the CCS's offsets (else: a device buffer of its own)
     const char *off;     // the accessor's refusal of a batch that ran without the output
     const char *failed;  // ... and of a ZMW without a result (null: it reads as length 0)
 };
 constexpr SideInfo kSide[kSideCount] = {
-    {1, 0, 0, 0, 0, true, "that batch ran with quality off (ccsx_gpu_set_quality)", nullptr},
-    {0, kPassWords * 4, 0, 0, 0, false, "that batch ran with pass statistics off (ccsx_gpu_set_pass_stats)",
+    {1, 0, 0, 0, 0, 0, true, "that batch ran with quality off (ccsx_gpu_set_quality)", nullptr},
+    {0, kPassWords * 4, 0, 0, 0, 0, false, "that batch ran with pass statistics off (ccsx_gpu_set_pass_stats)",
      "that ZMW failed: it has no pass statistics"},
-    {0, 0, 4, 0, 0, false, "that batch ran with the base map off (ccsx_gpu_set_base_map)",
+    {0, 0, 4, 0, 0, 0, false, "that batch ran with the base map off (ccsx_gpu_set_base_map)",
      "that ZMW failed: it has no base map"},
-    {kPuBytes, 0, 0, 1, 0, false, "that batch ran with the pileup off (ccsx_gpu_set_pileup)",
+    {kPuBytes, 0, 0, 1, 0, 0, false, "that batch ran with the pileup off (ccsx_gpu_set_pileup)",
      "that ZMW failed: it has no pileup"},
-    {kKnBytes, 0, 0, 1, 2, false, "that batch ran with kinetics off (ccsx_gpu_set_kinetics)",
+    {kKnBytes, 0, 0, 1, 2, 0, false, "that batch ran with kinetics off (ccsx_gpu_set_kinetics)",
      "that ZMW failed: it has no kinetics"},
+    // (bases and qualities of two strands: four bytes per byte of the output slab)
+    {4, 0, 0, 1, 0, kBysLenBytes, false, "that batch ran with the by-strand output off (ccsx_gpu_set_by_strand)",
+     "that ZMW failed: it has no strand consensus"},
 };
 
 // Bytes of output o's plane and, with its flags, the bytes it takes in a
 // fetched slice; with its device-only input (side_input) the bytes it adds to a
-// ZMW (its output slab, segments, pushed bases) or to a slice (their sums)
-inline uint64_t side_plane(int o, uint64_t slab, uint64_t nseg, uint64_t nbase)
+// ZMW (nz = 1, its output slab, segments, pushed bases) or to a slice of nz ZMWs
+// (their sums)
+inline uint64_t side_plane(int o, uint64_t nz, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
-    return kSide[o].per_slab * slab + kSide[o].per_seg * nseg + kSide[o].per_base * nbase;
+    return kSide[o].per_zmw * nz + kSide[o].per_slab * slab + kSide[o].per_seg * nseg + kSide[o].per_base * nbase;
 }
-inline uint64_t side_bytes(int o, uint64_t slab, uint64_t nseg, uint64_t nbase)
+inline uint64_t side_bytes(int o, uint64_t nz, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
-    return side_plane(o, slab, nseg, nbase) + kSide[o].flags_per_seg * nseg;
+    return side_plane(o, nz, slab, nseg, nbase) + kSide[o].flags_per_seg * nseg;
 }
 inline uint64_t side_input(int o, uint64_t nbase) { return uint64_t(kSide[o].in_per_base) * nbase; }
-inline uint64_t side_bytes_of(SideMask m, uint64_t slab, uint64_t nseg, uint64_t nbase)
+inline uint64_t side_bytes_of(SideMask m, uint64_t nz, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
     uint64_t b = 0;
     for (int o = 0; o < kSideCount; ++o)
-        if (m & side_bit(o)) b += side_bytes(o, slab, nseg, nbase);
+        if (m & side_bit(o)) b += side_bytes(o, nz, slab, nseg, nbase);
     return b;
 }
 // ... and what the outputs of m add to the device bytes of a ZMW or a slice
-inline uint64_t side_need_of(SideMask m, uint64_t slab, uint64_t nseg, uint64_t nbase)
+inline uint64_t side_need_of(SideMask m, uint64_t nz, uint64_t slab, uint64_t nseg, uint64_t nbase)
 {
-    uint64_t b = side_bytes_of(m, slab, nseg, nbase);
+    uint64_t b = side_bytes_of(m, nz, slab, nseg, nbase);
     for (int o = 0; o < kSideCount; ++o)
         if (m & side_bit(o)) b += side_input(o, nbase);
     return b;
@@ -89,15 +97,17 @@ struct SideLayout {
     uint64_t out_dev = 0;             // bytes of the device output buffer: the CCS plane and the in_out planes
     uint64_t total = 0;               // bytes of the host buffer
     bool has(int o) const { return (mask & side_bit(o)) != 0; }
-    void plan(SideMask m, uint64_t slab, uint64_t nseg, uint64_t nbase)
+    uint64_t nzmw = 0;                // ZMWs of the slice
+    void plan(SideMask m, uint64_t nz, uint64_t slab, uint64_t nseg, uint64_t nbase)
     {
         mask = m;
+        nzmw = nz;
         out_dev = total = slab;
         for (int o = 0; o < kSideCount; ++o) {
             plane[o] = bytes[o] = off[o] = 0;
             if (!has(o)) continue;
-            plane[o] = side_plane(o, slab, nseg, nbase);
-            bytes[o] = side_bytes(o, slab, nseg, nbase);
+            plane[o] = side_plane(o, nz, slab, nseg, nbase);
+            bytes[o] = side_bytes(o, nz, slab, nseg, nbase);
             off[o] = kSide[o].in_out ? total : (total + 7) & ~uint64_t(7);
             total = off[o] + bytes[o];
             if (kSide[o].in_out) out_dev = total;
@@ -105,7 +115,8 @@ struct SideLayout {
     }
 };
 // (an in_out plane behind an aligned one would not be fetched with the CCS)
-static_assert(kSide[0].in_out && !kSide[1].in_out && !kSide[2].in_out && !kSide[3].in_out && !kSide[4].in_out,
+static_assert(kSide[0].in_out && !kSide[1].in_out && !kSide[2].in_out && !kSide[3].in_out && !kSide[4].in_out &&
+                  !kSide[5].in_out,
               "in_out planes come first");
 
 // One ZMW's results where they lie, in a fetched slice or a gathered batch; the
@@ -121,6 +132,9 @@ struct SideRec {
     const uint32_t *seg_at = nullptr;   // with map: nseg word offsets into map (null: the lengths' running sum)
     const ccsx_pileup *pile = nullptr;  // len records
     const ccsx_kinetics *kin = nullptr;  // len records
+    // the strand consensuses (SPEC.md §14), forward then reverse: slen[s] bases and as many quality bytes
+    const uint8_t *sseq[2] = {nullptr, nullptr}, *squal[2] = {nullptr, nullptr};
+    uint32_t slen[2] = {0, 0};
     // segment k of the map
     const uint32_t *map_seg(uint32_t k) const
     {
@@ -160,6 +174,16 @@ struct SideView {
         }
         if (lay->has(kSidePile)) r.pile = reinterpret_cast<const ccsx_pileup *>(h_out + lay->off[kSidePile]) + d.out_off;
         if (lay->has(kSideKin)) r.kin = reinterpret_cast<const ccsx_kinetics *>(h_out + lay->off[kSideKin]) + d.out_off;
+        if (lay->has(kSideStrand)) {
+            // the pairs of lengths, then per ZMW four slabs of its outcap bytes
+            const uint8_t *pl = h_out + lay->off[kSideStrand];
+            const uint8_t *zp = pl + uint64_t(kBysLenBytes) * lay->nzmw + 4 * d.out_off;
+            for (int s = 0; s < 2; ++s) {
+                r.slen[s] = r.ok ? reinterpret_cast<const uint32_t *>(pl)[2 * i + s] : 0;
+                r.sseq[s] = zp + size_t(2 * s) * d.outcap;
+                r.squal[s] = zp + size_t(2 * s + 1) * d.outcap;
+            }
+        }
         return r;
     }
 };
@@ -170,12 +194,13 @@ struct SideView {
 struct Gathered {
     struct At {
         uint64_t ccs = 0, pass = 0, map = 0, seg = 0;  // offsets into arena (qual, pile, kin), pass, map, seg_len (seg_at)
-        uint32_t len = 0, nseg = 0;
+        uint64_t str = 0;  // ... and into sseq / squal: the forward strand's bytes, the reverse strand's behind them
+        uint32_t len = 0, nseg = 0, slen[2] = {0, 0};
         bool ok = false;
     };
     SideMask mask = 0;
     std::vector<At> at;               // per ZMW
-    std::vector<uint8_t> arena, qual;
+    std::vector<uint8_t> arena, qual, sseq, squal;
     std::vector<uint32_t> pass, map;
     std::vector<uint32_t> seg_len, seg_at;  // per gathered segment of the map: entries, word offset in its ZMW's map
     std::vector<ccsx_pileup> pile;
@@ -188,6 +213,7 @@ struct Gathered {
         mask = m;
         at.assign(nz, At{});
         arena.clear(), qual.clear(), pass.clear(), map.clear(), seg_len.clear(), seg_at.clear(), pile.clear(), kin.clear();
+        sseq.clear(), squal.clear();
     }
     // one growth per slice of `add` CCS bytes, not one per ZMW's append (~150
     // MB for a 10k-ZMW slice of 15 kb inserts)
@@ -221,9 +247,17 @@ struct Gathered {
         }
         if (has(kSidePile)) pile.insert(pile.end(), r.pile, r.pile + r.len);
         if (has(kSideKin)) kin.insert(kin.end(), r.kin, r.kin + r.len);
+        if (has(kSideStrand)) {
+            a.str = sseq.size();
+            for (int s = 0; s < 2; ++s) {
+                a.slen[s] = r.slen[s];
+                sseq.insert(sseq.end(), r.sseq[s], r.sseq[s] + r.slen[s]);
+                squal.insert(squal.end(), r.squal[s], r.squal[s] + r.slen[s]);
+            }
+        }
     }
     // ZMW g is reported as failed after all: without a result in every output
-    void drop(size_t g) { at[g].ok = false, at[g].len = 0; }
+    void drop(size_t g) { at[g].ok = false, at[g].len = 0, at[g].slen[0] = at[g].slen[1] = 0; }
     const char *ccs(size_t g) const { return reinterpret_cast<const char *>(arena.data() + at[g].ccs); }
     SideRec rec(size_t g) const
     {
@@ -237,6 +271,11 @@ struct Gathered {
         if (has(kSideMap)) r.map = map.data() + a.map, r.seg_len = seg_len.data() + a.seg, r.seg_at = seg_at.data() + a.seg;
         if (has(kSidePile)) r.pile = pile.data() + a.ccs;
         if (has(kSideKin)) r.kin = kin.data() + a.ccs;
+        if (has(kSideStrand))
+            for (int s = 0; s < 2; ++s) {
+                const uint64_t o = a.str + (s ? a.slen[0] : 0);
+                r.slen[s] = a.slen[s], r.sseq[s] = sseq.data() + o, r.squal[s] = squal.data() + o;
+            }
         return r;
     }
 };

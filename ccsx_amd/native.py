@@ -32,7 +32,7 @@ EXPORTS = {
                    "ccsx_gpu_slot_bytes", "ccsx_gpu_submit", "ccsx_gpu_collect", "ccsx_gpu_reserve_staging",
                    "ccsx_gpu_set_quality", "ccsx_gpu_quality", "ccsx_gpu_set_pass_stats", "ccsx_gpu_pass_stats",
                    "ccsx_gpu_set_base_map", "ccsx_gpu_base_map", "ccsx_gpu_set_pileup", "ccsx_gpu_pileup",
-                   "ccsx_gpu_set_kinetics", "ccsx_gpu_kinetics",
+                   "ccsx_gpu_set_kinetics", "ccsx_gpu_kinetics", "ccsx_gpu_set_by_strand", "ccsx_gpu_by_strand",
                    "ccsx_gpu_aln_open", "ccsx_gpu_aln_close", "ccsx_gpu_aln_error", "ccsx_gpu_band_align",
                    "ccsx_gpu_aln_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
@@ -153,6 +153,10 @@ def lib() -> C.CDLL:
         L.ccsx_gpu_set_pileup.argtypes = [C.c_void_p, C.c_int]
         L.ccsx_gpu_pileup.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.ccsx_pileup_call.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "ccsx_gpu_set_by_strand"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_gpu_set_by_strand.argtypes = [C.c_void_p, C.c_int]
+            L.ccsx_gpu_by_strand.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         if hasattr(L, "ccsx_gpu_set_kinetics"):  # (absent from the older builds used in A/B runs)
             L.ccsx_gpu_set_kinetics.argtypes = [C.c_void_p, C.c_int]
             L.ccsx_gpu_kinetics.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
@@ -261,7 +265,7 @@ def synth_zmw(seed: int, hole: int, L: int, passes: int):
 class Prepared:
     """One ZMW after ccs_prepare + strand flip: segments are slices of seqs;
     rev = ccs_prepare's strand flag per segment (None: all forward), read by the
-    engine only with the strand pileup or the kinetics on; ipd / pw = one 8-bit
+    engine only with the strand pileup, the kinetics or the by-strand output on; ipd / pw = one 8-bit
     kinetics code per byte of seqs in the orientation the segments are pushed in
     (SPEC.md §13; None: the ZMW has none), read only with the kinetics on."""
     seqs: bytes
@@ -958,6 +962,29 @@ class Engine:
         if not n.value:
             return np.zeros((0, 8), np.uint8)
         return np.frombuffer(C.string_at(p, n.value * 8), dtype=np.uint8).reshape(n.value, 8).copy()
+
+    def set_by_strand(self, on: bool = True) -> None:
+        """The per-strand consensus for the following stage / run / submit calls
+        (ccsx_gpu_set_by_strand): the sequence each strand's reads support in
+        the MSA the CCS was called from (SPEC.md §14), read with by_strand()."""
+        if self._L.ccsx_gpu_set_by_strand(self._ctx, 1 if on else 0) != 0:
+            self._err("ccsx_gpu_set_by_strand")
+
+    def by_strand(self, i: int, slot: int = -1):
+        """The strand consensuses of ZMW i: (forward bases, forward qualities
+        uint8 [len_fwd], reverse bases, reverse qualities uint8 [len_rev]), both
+        in the CCS's orientation, a strand without a pushed segment empty: of
+        the last run() / fetch() (slot -1) or of the batch collected from
+        `slot`; raises if that batch ran with the output off or the ZMW failed."""
+        out = []
+        for strand in (0, 1):
+            p, q = C.c_void_p(), C.c_void_p()
+            n = C.c_uint32(0)
+            if self._L.ccsx_gpu_by_strand(self._ctx, slot, i, strand, C.byref(p), C.byref(q), C.byref(n)) != 0:
+                self._err("ccsx_gpu_by_strand")
+            out.append(C.string_at(p, n.value) if n.value else b"")
+            out.append(np.frombuffer(C.string_at(q, n.value), dtype=np.uint8).copy() if n.value else np.zeros(0, np.uint8))
+        return tuple(out)
 
     def set_fault(self, i: int) -> None:
         """Test hook (ccsx_gpu_set_fault): the next run() / submit() reports ZMW

@@ -44,7 +44,8 @@ typedef struct {
     const uint32_t *seg_len;  /* nseg lengths */
     uint32_t nseg;
     const uint8_t *seg_rev;   /* nseg strand flags (1: ccs_prepare marked the segment reverse), or NULL = all
-                               * forward; read only with ccsx_gpu_set_pileup or ccsx_gpu_set_kinetics on */
+                               * forward; read only with ccsx_gpu_set_pileup, ccsx_gpu_set_kinetics or
+                               * ccsx_gpu_set_by_strand on */
     const uint8_t *ipd;       /* the 8-bit inter-pulse duration code of every base, parallel to seqs and in the
                                * orientation the segments are pushed in (SPEC.md section 13), or NULL = none;
                                * read only with ccsx_gpu_set_kinetics on */
@@ -262,6 +263,42 @@ typedef struct {
 } ccsx_kinetics;
 int ccsx_gpu_set_kinetics(ccsx_ctx *ctx, int on);
 int ccsx_gpu_kinetics(ccsx_ctx *ctx, int slot, size_t zmw, const ccsx_kinetics **rec, uint32_t *len);
+/* Per-strand consensus (SPEC.md section 14), off by default: the sequence each
+ * strand's reads support (ccsx_zmw_in::seg_rev; NULL = all forward), read off
+ * the MSA the CCS was called from -- not a second POA over one strand's reads.
+ * In every emitted column the strand's reads span, section 6's rule on that
+ * strand's counts (the rule ccsx_pileup_call applies to a pileup record) calls
+ * a base or a gap; the strand's consensus is the called bases in emission
+ * order, columns the joint consensus dropped included, each with section 9's
+ * quality from the strand's counts.  Both strands are in the CCS's orientation:
+ * nothing is reverse-complemented.
+ * on != 0: the following ccsx_gpu_stage* / ccsx_gpu_run / ccsx_gpu_submit calls
+ * give every ZMW four bytes per byte of its output slab (bases and qualities of
+ * two strands) and two length words, device and pinned host, written once per
+ * launch by the kernel's emission and copied back with the CCS, and a strand
+ * flag byte per segment beside them.  A strand consensus longer than the tight
+ * output slab fails the ZMW like a CCS that is (the full-capacity re-run then
+ * holds it: the full slab is at least the pushed bases).  With the output on,
+ * ccsx_gpu_zmw_bytes, the batch size ccsx_gpu_submit checks against
+ * ccsx_gpu_slot_bytes and ccsx_gpu_staged_bytes include exactly 4 x the ZMW's
+ * output slab + nseg + 8 per ZMW (a caller sizing ccsx_gpu_reserve_staging adds
+ * the same to its out_bytes); with it off those values, the kernels launched
+ * and the bytes copied are what they are without this call.  Independent of the
+ * other five outputs.  A batch keeps the setting it was staged or submitted
+ * with (the full-capacity re-run inside ccsx_gpu_collect included).  The
+ * bspoa-compatible single-POA mode (ccsx_bspoa.h) has no strand consensus.
+ * ccsx_gpu_by_strand: the consensus of strand `strand` (0 forward, 1 reverse)
+ * of ZMW `zmw` of a batch: *len ASCII bases at *seq (not NUL-terminated) and
+ * *len quality bytes (0 .. 93, not ASCII) at *qual; *len = 0 for a strand
+ * without a pushed segment.  slot -1 = the last ccsx_gpu_run or ccsx_gpu_fetch
+ * on this context, 0 / 1 = that slot's last collected ccsx_gpu_submit batch.
+ * ctx-owned, valid as long as that batch's out[i].ccs.  Returns -1
+ * (ccsx_gpu_error says why) if the batch ran with the output off, is not
+ * collected yet, has no ZMW `zmw`, that ZMW failed (status != 0), or strand is
+ * neither 0 nor 1. */
+int ccsx_gpu_set_by_strand(ccsx_ctx *ctx, int on);
+int ccsx_gpu_by_strand(ccsx_ctx *ctx, int slot, size_t zmw, int strand, const char **seq, const uint8_t **qual,
+                       uint32_t *len);
 /* The same in three steps (one slice, tight capacities, no re-run), so inputs
  * can stay resident in HBM across launches (used by bench.py).
  * ccsx_gpu_launch returns the kernel time measured with HIP events on the
@@ -277,8 +314,8 @@ int ccsx_gpu_fetch(ccsx_ctx *ctx, ccsx_zmw_out *out);
 
 /* Device bytes the staged batch occupies (workspace + arenas; the quality
  * plane, the pass records, the base map, the strand pileup with its strand
- * flags and the kinetics records with their input planes and strand bytes when
- * the batch has them). */
+ * flags, the kinetics records with their input planes and strand bytes and the
+ * by-strand plane with its lengths and strand flags when the batch has them). */
 uint64_t ccsx_gpu_staged_bytes(const ccsx_ctx *ctx);
 
 /* Diagnostics: per-phase shader-clock counters (s_memtime) summed over the
@@ -340,7 +377,8 @@ int ccsx_gpu_set_mem_wait(ccsx_ctx *ctx, uint32_t ms);
  * tables, 24 bytes per segment with pass statistics on, 4 bytes per pushed
  * base with the base map on, 12 bytes per output slab byte and one per segment
  * with the strand pileup on, 8 bytes per output slab byte, 2 per pushed base
- * and one per segment with kinetics on). */
+ * and one per segment with kinetics on, 4 bytes per output slab byte, one per
+ * segment and 8 with the by-strand output on). */
 uint64_t ccsx_gpu_zmw_bytes(const ccsx_ctx *ctx, int mode, const ccsx_zmw_in *z);
 /* Test hook: bytes per slot for ccsx_gpu_run's slices (0 = by device memory:
  * half of this context's share, ccsx_gpu_set_mem_share), so a small batch is

@@ -20,7 +20,7 @@
 
 static uint32_t crc(const char *p, size_t n) { return (uint32_t)crc32(0, reinterpret_cast<const unsigned char *>(p), (uInt)n); }
 
-// side_out.h on synthetic slices of 0, 1 and 5 ZMWs under all 16 masks: a ZMW
+// side_out.h on synthetic slices of 0, 1 and 5 ZMWs under all 64 masks: a ZMW
 // without a segment, one with an odd output slab (the slice's slabs then end off
 // a multiple of 8), one with an empty segment, one failed.  Returns 0 or the
 // number of the check that failed.
@@ -34,7 +34,8 @@ static int side_outputs()
     const std::vector<Z> five = {{{7, 5, 9}, 40, 0}, {{}, 16, 0}, {{4, 0}, 33, 0}, {{11}, 24, kErrOut}, {{3, 3, 3, 2}, 32, 0}};
     const std::vector<Z> one = {five[2]};
     const size_t perm5[5] = {2, 4, 0, 3, 1};
-    const size_t align[kSideCount] = {1, alignof(uint32_t), alignof(uint32_t), alignof(ccsx_pileup), alignof(ccsx_kinetics)};
+    const size_t align[kSideCount] = {1, alignof(uint32_t), alignof(uint32_t), alignof(ccsx_pileup), alignof(ccsx_kinetics),
+                                      alignof(uint32_t)};
     for (SideMask m = 0; m <= kSideAll; ++m)
         for (const std::vector<Z> *zs : {(const std::vector<Z> *)nullptr, &one, &five}) {
             const size_t nz = zs ? zs->size() : 0;
@@ -55,7 +56,7 @@ static int side_outputs()
                 map_off[i] = nbase;
                 status[i] = (int32_t)z.status;
                 out_len[i] = z.outcap - 3;
-                for (int o = 0; o < kSideCount; ++o) per_zmw[o] += side_bytes(o, z.outcap, z.lens.size(), S);
+                for (int o = 0; o < kSideCount; ++o) per_zmw[o] += side_bytes(o, 1, z.outcap, z.lens.size(), S);
                 seg_len.insert(seg_len.end(), z.lens.begin(), z.lens.end());
                 slab += z.outcap, nbase += S;
             }
@@ -63,15 +64,15 @@ static int side_outputs()
             // sizes: a slice's is the sum of its ZMWs', per output and for the mask
             uint64_t sum = 0;
             for (int o = 0; o < kSideCount; ++o) {
-                if (side_bytes(o, slab, seg_len.size(), nbase) != per_zmw[o]) return 51;
+                if (side_bytes(o, nz, slab, seg_len.size(), nbase) != per_zmw[o]) return 51;
                 if (m & side_bit(o)) sum += per_zmw[o];
             }
-            if (side_bytes_of(m, slab, seg_len.size(), nbase) != sum) return 52;
+            if (side_bytes_of(m, nz, slab, seg_len.size(), nbase) != sum) return 52;
             // layout: the planes in order, none overlapping, each aligned for its
             // elements, less than 8 bytes of padding before each; the total is
             // the CCS plane, the enabled outputs and that padding
             SideLayout L;
-            L.plan(m, slab, seg_len.size(), nbase);
+            L.plan(m, nz, slab, seg_len.size(), nbase);
             uint64_t end = slab, pad = 0;
             for (int o = 0; o < kSideCount; ++o) {
                 if (!(m & side_bit(o))) {
@@ -79,7 +80,7 @@ static int side_outputs()
                     continue;
                 }
                 if (!L.has(o) || L.off[o] < end || L.off[o] - end >= 8 || L.off[o] % align[o]) return 54;
-                if (L.bytes[o] != side_bytes(o, slab, seg_len.size(), nbase) || L.plane[o] > L.bytes[o]) return 55;
+                if (L.bytes[o] != side_bytes(o, nz, slab, seg_len.size(), nbase) || L.plane[o] > L.bytes[o]) return 55;
                 if (kSide[o].in_out && (L.off[o] != end || L.out_dev != L.off[o] + L.plane[o])) return 56;
                 pad += L.off[o] - end;
                 end = L.off[o] + L.bytes[o];
@@ -89,6 +90,15 @@ static int side_outputs()
             // bytes, so a read past a plane's end is one past the allocation)
             std::vector<uint8_t> h(L.total);
             for (size_t j = 0; j < h.size(); ++j) h[j] = uint8_t(j * 131 + m * 7 + 1);
+            // the by-strand plane's lengths are read as lengths: one strand fills
+            // its slab to the last byte, the other is empty or a byte long
+            auto strand_len = [&](size_t i, int s) { return s == int(i & 1) ? desc[i].outcap : uint32_t(i % 3 == 0); };
+            if (L.has(kSideStrand))
+                for (size_t i = 0; i < nz; ++i)
+                    for (int s = 0; s < 2; ++s) {
+                        const uint32_t v = strand_len(i, s);
+                        memcpy(h.data() + L.off[kSideStrand] + (2 * i + s) * 4, &v, 4);
+                    }
             const SideView v{&L, h.data(), nz, desc.data(), seg_len.data(), map_off.data(), status.data(), out_len.data()};
             // gathered in a permuted input order: ZMW i of the slice is input perm[i]
             Gathered G;
@@ -128,6 +138,13 @@ static int side_outputs()
                             return 64;
                         if (o == kSidePile && memcmp(r[k].pile, h.data() + L.off[o] + d.out_off * kPuBytes, size_t(r[k].len) * kPuBytes))
                             return 65;
+                        if (o == kSideStrand)
+                            for (int s = 0; s < 2; ++s) {
+                                const uint8_t *zp = h.data() + L.off[o] + kBysLenBytes * nz + 4 * d.out_off;
+                                if (r[k].slen[s] != strand_len(i, s)) return 69;
+                                if (memcmp(r[k].sseq[s], zp + size_t(2 * s) * d.outcap, r[k].slen[s])) return 70;
+                                if (memcmp(r[k].squal[s], zp + size_t(2 * s + 1) * d.outcap, r[k].slen[s])) return 71;
+                            }
                         if (o == kSideMap) {
                             uint64_t at = map_off[i];
                             for (uint32_t s = 0; s < d.n; ++s) {
@@ -143,7 +160,8 @@ static int side_outputs()
                 G.drop(perm[0]);
                 for (int o = 0; o < kSideCount; ++o) {
                     SideRec r;
-                    if ((m & side_bit(o)) && (side_find(G, o, perm[0], r) != kSide[o].failed || r.ok || r.len)) return 68;
+                    if ((m & side_bit(o)) && (side_find(G, o, perm[0], r) != kSide[o].failed || r.ok || r.len || r.slen[0] || r.slen[1]))
+                        return 68;
                 }
             }
         }

@@ -3,7 +3,7 @@
 // the BAM aux parser of the ingest (at block sizes down to 1 byte, on records
 // with well-formed, missing, miscounted and cut-short ip / pw arrays),
 // ccsx_prepare_apply_kin, ccsx_kinetics_tags, and the kinetics output's
-// bookkeeping in side_out.h under all 32 masks.  tests/test_kinetics_sanitize.py
+// bookkeeping in side_out.h under all 32 masks of the first five outputs.  tests/test_kinetics_sanitize.py
 // compiles it with the host sources it needs (no HIP code is involved).
 //   kinetics_sanitize FILE.bam ...   prints one line per ZMW read
 #include <zlib.h>
@@ -21,7 +21,8 @@
 static uint32_t crc(const void *p, size_t n) { return (uint32_t)crc32(0, static_cast<const unsigned char *>(p), (uInt)n); }
 
 // side_out.h with the fifth output: sizes (the per-base input counts on the
-// device only), the plane's place in a slice, gathering and lookup
+// device only), the plane's place in a slice, gathering and lookup, under every
+// subset of the first five outputs (tools/host_sanitize.cpp walks the later ones)
 static int side_outputs()
 {
     using namespace ccsx;
@@ -31,7 +32,8 @@ static int side_outputs()
     };
     const std::vector<Z> zs = {{{7, 5, 9}, 40, 0}, {{}, 16, 0}, {{4, 0}, 33, 0}, {{11}, 24, kErrOut}, {{3, 3, 3, 2}, 32, 0}};
     const size_t nz = zs.size();
-    for (SideMask m = 0; m <= kSideAll; ++m) {
+    const SideMask five = side_bit(kSideKin + 1) - 1;
+    for (SideMask m = 0; m <= five; ++m) {
         std::vector<ZmwDesc> desc(nz);
         std::vector<uint32_t> seg_len, out_len(nz);
         std::vector<uint64_t> map_off(nz);
@@ -43,19 +45,20 @@ static int side_outputs()
             desc[i].seg0 = (uint32_t)seg_len.size(), desc[i].n = (uint32_t)zs[i].lens.size();
             desc[i].out_off = slab, desc[i].outcap = zs[i].outcap;
             map_off[i] = nbase, status[i] = (int32_t)zs[i].status, out_len[i] = zs[i].outcap - 3;
-            need += side_need_of(m, zs[i].outcap, zs[i].lens.size(), S);
-            if (side_need_of(m, zs[i].outcap, zs[i].lens.size(), S) - side_need_of(m & ~side_bit(kSideKin), zs[i].outcap, zs[i].lens.size(), S) !=
+            need += side_need_of(m, 1, zs[i].outcap, zs[i].lens.size(), S);
+            if (side_need_of(m, 1, zs[i].outcap, zs[i].lens.size(), S) -
+                    side_need_of(m & ~side_bit(kSideKin), 1, zs[i].outcap, zs[i].lens.size(), S) !=
                 ((m & side_bit(kSideKin)) ? 8ull * zs[i].outcap + 2 * S + zs[i].lens.size() : 0ull))
                 return 70;
             seg_len.insert(seg_len.end(), zs[i].lens.begin(), zs[i].lens.end());
             slab += zs[i].outcap, nbase += S;
         }
-        if (side_need_of(m, slab, seg_len.size(), nbase) != need) return 71;
-        if (side_need_of(m, slab, seg_len.size(), nbase) !=
-            side_bytes_of(m, slab, seg_len.size(), nbase) + ((m & side_bit(kSideKin)) ? 2 * nbase : 0))
+        if (side_need_of(m, nz, slab, seg_len.size(), nbase) != need) return 71;
+        if (side_need_of(m, nz, slab, seg_len.size(), nbase) !=
+            side_bytes_of(m, nz, slab, seg_len.size(), nbase) + ((m & side_bit(kSideKin)) ? 2 * nbase : 0))
             return 72;
         SideLayout L;
-        L.plan(m, slab, seg_len.size(), nbase);
+        L.plan(m, nz, slab, seg_len.size(), nbase);
         if (L.has(kSideKin) && (L.plane[kSideKin] != slab * kKnBytes || L.bytes[kSideKin] != L.plane[kSideKin] + seg_len.size() ||
                                 L.off[kSideKin] % 8 || L.off[kSideKin] + L.bytes[kSideKin] != L.total))
             return 73;
@@ -83,7 +86,7 @@ static int side_outputs()
             }
         }
     }
-    printf("side outputs %d masks\n", (int)kSideAll + 1);
+    printf("side outputs %d masks\n", (int)five + 1);
     return 0;
 }
 
