@@ -127,6 +127,7 @@ struct Zmw {
     std::string paf;          // -a: the PAF lines of its segments (SPEC.md section 11)
     std::string sites;        // -s: the lines of its discordant sites (SPEC.md section 12)
     std::string strands;      // -b: the records of its strand consensuses (SPEC.md section 14)
+    std::string polished;     // -p: the record of its polished read (SPEC.md section 15)
     std::vector<uint8_t> kin;  // -k: the ipd codes of its bases, then the pw codes, parallel to seqs (empty: a subread lacks them)
     std::string kinline;      // -k: its SAM line (SPEC.md section 13)
     bool kin_arrays = false;  // -k: ... carries the four arrays
@@ -177,6 +178,7 @@ int usage()
             "-a     <file>  Subread-to-CCS alignments (PAF, cg:Z: with =/X/I/D): per subread, where its bases lie in the CCS by the alignment the CCS was called from \n"
             "-s     <file>  Strand-discordant sites (tab-separated): per CCS position whose forward and reverse subreads call different bases (or base against gap), the two calls and the per-strand A/C/G/T/gap/ins counts \n"
             "-b     <file>  Per-strand consensus (fasta, fastq with -q): per CCS read the sequence its forward and its reverse subreads support in the alignment the CCS was called from, as <name>/fwd and <name>/rev in the CCS's orientation \n"
+            "-p     <file>  Polished reads (fasta, fastq with -q): per CCS read, every subread realigned to the finished CCS on the GPU and the bases voted again per position, as <name>/polished; the main output and the other files stay the draft's \n"
             "-k     <file>  Consensus kinetics (unaligned SAM; BAM input only): per CCS read its bases, np/fn/rn and, from the subreads' ip/pw tags, the per-strand mean inter-pulse duration and pulse width per base as fi/fp/ri/rp B:C arrays \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
@@ -559,10 +561,11 @@ int main(int argc, char **argv)
     const char *site_path = nullptr;    // -s
     const char *kin_path = nullptr;     // -k
     const char *strand_path = nullptr;  // -b
+    const char *polish_path = nullptr;  // -p
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -574,6 +577,7 @@ int main(int argc, char **argv)
         case 's': site_path = optarg; break;
         case 'k': kin_path = optarg; break;
         case 'b': strand_path = optarg; break;
+        case 'p': polish_path = optarg; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -645,6 +649,11 @@ int main(int argc, char **argv)
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
+    FILE *fp_pol = polish_path ? fopen(polish_path, "w") : nullptr;
+    if (polish_path && !fp_pol) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
     if (fp_kin) fprintf(fp_kin, "@HD\tVN:1.6\tSO:unknown\n");
     if (fp_rep) fprintf(fp_rep, "#name\tpass\tsbeg\tslen\tmatch\tmismatch\tins\tdel\tcbeg\tcend\tidentity\n");
     // step 1 pipelined per context (ccsx_gpu_submit / ccsx_gpu_collect: the
@@ -698,6 +707,10 @@ int main(int argc, char **argv)
     const bool timing = getenv("CCSX_TIMING") && atoi(getenv("CCSX_TIMING"));
     const bool gpu_strand = getenv("CCSX_GPU_STRAND") && atoi(getenv("CCSX_GPU_STRAND"));
     ccsx_aln_ctx *aln = nullptr;
+    // -p: the one polisher context, on the first GPU; its results hold until
+    // its next call, so a worker keeps pol_m from its call until it has copied them
+    ccsx_polish_ctx *pol = nullptr;
+    std::mutex pol_m;
     bool aln_tried = false;
     const auto tstart = std::chrono::steady_clock::now();
     auto now_ms = [tstart]() {
@@ -904,6 +917,54 @@ int main(int argc, char **argv)
                 if (verbose > 2 && !f.out[i].status && ccsx_gpu_bp_log(ctx[w], i, &lg, &nr) == 0)
                     z.bp.assign(lg, lg + 2 * (size_t)nr);
             }
+            if (pol && !qfail) {
+                // -p: the batch's ZMWs with a CCS, their drafts and maps as collected
+                std::vector<ccsx_polish_in> pin;
+                std::vector<size_t> who;
+                std::vector<std::vector<uint32_t>> maps;
+                for (size_t i = 0; i < f.b.idx.size() && !qfail; ++i) {
+                    Zmw &z = ch.zs[f.b.idx[i]];
+                    if (f.out[i].status || z.ccs.empty()) continue;
+                    std::vector<uint32_t> m;
+                    for (size_t k = 0; k < z.seg_len.size(); ++k) {
+                        const uint32_t *mp = nullptr;
+                        uint32_t ml = 0;
+                        if (ccsx_gpu_base_map(ctx[w], f.slot, i, (uint32_t)k, &mp, &ml) != 0 || ml != z.seg_len[k]) {
+                            qfail = true;
+                            break;
+                        }
+                        m.insert(m.end(), mp, mp + ml);
+                    }
+                    pin.push_back(ccsx_polish_in{z.ccs.data(), (uint32_t)z.ccs.size(), z.seqs, z.seg_off.data(), z.seg_len.data(),
+                                                 (uint32_t)z.seg_len.size(), nullptr});
+                    who.push_back(f.b.idx[i]);
+                    maps.push_back(std::move(m));
+                }
+                for (size_t i = 0; i < pin.size(); ++i) pin[i].map = maps[i].data();
+                if (!qfail && !pin.empty()) {
+                    std::vector<ccsx_polish_out> po(pin.size());
+                    std::lock_guard<std::mutex> g(pol_m);
+                    if (ccsx_gpu_polish(pol, pin.data(), pin.size(), po.data(), nullptr) != 0) {
+                        std::lock_guard<std::mutex> g2(err_m);
+                        fprintf(stderr, "[ccsx] polisher: %s\n", ccsx_gpu_polish_error(pol));
+                        qfail = true;
+                    }
+                    for (size_t i = 0; i < pin.size() && !qfail; ++i) {
+                        Zmw &z = ch.zs[who[i]];
+                        if (po[i].status || !po[i].len) continue;  // (a collected map is never a bad one)
+                        std::string &s = z.polished;
+                        s += fastq ? '@' : '>';
+                        s += z.movie + "/" + z.hole + "/ccs/polished\n";
+                        s.append(po[i].seq, po[i].len);
+                        s += '\n';
+                        if (fastq) {
+                            s += "+\n";
+                            for (uint32_t k = 0; k < po[i].len; ++k) s += (char)(po[i].qual[k] + 33);
+                            s += '\n';
+                        }
+                    }
+                }
+            }
         }
         if ((qfail || (r != 0 && r != -2)) && !fatal.exchange(true)) {
             std::lock_guard<std::mutex> g(err_m);
@@ -1094,7 +1155,7 @@ int main(int argc, char **argv)
             if (verbose > 2 && split_subread) ccsx_gpu_set_bp_log(ctx[i], 1);
             if (fastq) ccsx_gpu_set_quality(ctx[i], 1);
             if (fp_rep) ccsx_gpu_set_pass_stats(ctx[i], 1);
-            if (fp_paf) ccsx_gpu_set_base_map(ctx[i], 1);
+            if (fp_paf || fp_pol) ccsx_gpu_set_base_map(ctx[i], 1);
             if (fp_site) ccsx_gpu_set_pileup(ctx[i], 1);
             if (fp_kin) ccsx_gpu_set_kinetics(ctx[i], 1);
             if (fp_str) ccsx_gpu_set_by_strand(ctx[i], 1);
@@ -1104,6 +1165,7 @@ int main(int argc, char **argv)
                 (mem_frac > 0.f && ccsx_gpu_set_mem_frac(ctx[i], mem_frac) != 0))
                 die("invalid CCSX_KCFG / CCSX_WG_PER_CU / CCSX_SHRED_READ_CAP / CCSX_MEM_FRAC");
         }
+        if (fp_pol && ccsx_gpu_polish_open(0, 0, &pol) != 0) die("cannot open the polisher context");
         // pipelined: batches of at most ~95 % of a slot (ccsx_gpu_slot_bytes),
         // so a submitted batch always fits one launch
         if (async && ccsx_gpu_slot_bytes(ctx[0], &slot_bytes) != 0) die(ccsx_gpu_error(ctx[0]));
@@ -1170,6 +1232,7 @@ int main(int argc, char **argv)
                     if (fp_paf) fwrite(z.paf.data(), 1, z.paf.size(), fp_paf);
                     if (fp_site) fwrite(z.sites.data(), 1, z.sites.size(), fp_site);
                     if (fp_str) fwrite(z.strands.data(), 1, z.strands.size(), fp_str);
+                    if (fp_pol) fwrite(z.polished.data(), 1, z.polished.size(), fp_pol);
                     if (fp_kin) {
                         if (!z.kin_arrays) ++nokin;
                         fwrite(z.kinline.data(), 1, z.kinline.size(), fp_kin);
@@ -1260,6 +1323,7 @@ int main(int argc, char **argv)
         if (fp_site) werr = (ferror(fp_site) || fclose(fp_site) != 0) || werr;
         if (fp_kin) werr = (ferror(fp_kin) || fclose(fp_kin) != 0) || werr;
         if (fp_str) werr = (ferror(fp_str) || fclose(fp_str) != 0) || werr;
+        if (fp_pol) werr = (ferror(fp_pol) || fclose(fp_pol) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1295,6 +1359,7 @@ int main(int argc, char **argv)
     for (auto &t : workers) t.join();
     for (auto *x : ctx) ccsx_gpu_close(x);
     ccsx_gpu_aln_close(aln);
+    ccsx_gpu_polish_close(pol);
     reap.push(nullptr);
     reaper.join();
     if (timing) fprintf(stderr, "[ccsx] output done at %.0f ms, contexts closed at %.0f ms\n", tw, now_ms());
@@ -1306,6 +1371,7 @@ int main(int argc, char **argv)
     if (fp_site) (void)fclose(fp_site);
     if (fp_kin) (void)fclose(fp_kin);
     if (fp_str) (void)fclose(fp_str);
+    if (fp_pol) (void)fclose(fp_pol);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

@@ -34,11 +34,13 @@ EXPORTS = {
                    "ccsx_gpu_set_base_map", "ccsx_gpu_base_map", "ccsx_gpu_set_pileup", "ccsx_gpu_pileup",
                    "ccsx_gpu_set_kinetics", "ccsx_gpu_kinetics", "ccsx_gpu_set_by_strand", "ccsx_gpu_by_strand",
                    "ccsx_gpu_aln_open", "ccsx_gpu_aln_close", "ccsx_gpu_aln_error", "ccsx_gpu_band_align",
-                   "ccsx_gpu_aln_stats"],
+                   "ccsx_gpu_aln_stats",
+                   "ccsx_gpu_polish_open", "ccsx_gpu_polish_close", "ccsx_gpu_polish_error", "ccsx_gpu_polish",
+                   "ccsx_gpu_polish_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
-                    "ccsx_map_cigar", "ccsx_pileup_call",
+                    "ccsx_map_cigar", "ccsx_pileup_call", "ccsx_polish_host",
                     "ccsx_prepare_apply_kin", "ccsx_kin_frames", "ccsx_kin_code", "ccsx_kinetics_tags",
                     "ccsx_synth_batch_kinetics",
                     "ccsx_pairwise_seed", "ccsx_pairwise_band", "ccsx_prep_begin", "ccsx_prep_pending",
@@ -68,6 +70,16 @@ class Pair(C.Structure):
 
 class BandJob(C.Structure):
     _fields_ = [("q", C.c_char_p), ("t", C.c_char_p), ("qlen", C.c_uint32), ("tlen", C.c_uint32), ("d0", C.c_int32)]
+
+
+class PolishIn(C.Structure):
+    _fields_ = [("ccs", C.c_char_p), ("len", C.c_uint32), ("seqs", C.c_char_p), ("seg_off", C.POINTER(C.c_uint32)),
+                ("seg_len", C.POINTER(C.c_uint32)), ("nseg", C.c_uint32), ("map", C.POINTER(C.c_uint32))]
+
+
+class PolishOut(C.Structure):
+    _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("len", C.c_uint32), ("nsub", C.c_uint32),
+                ("nins", C.c_uint32), ("ndel", C.c_uint32), ("map", C.POINTER(C.c_uint32)), ("status", C.c_int32)]
 
 
 class BatchInfo(C.Structure):
@@ -208,6 +220,19 @@ def lib() -> C.CDLL:
                                              C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
                                              C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32),
                                              C.POINTER(BatchInfo)]
+        if hasattr(L, "ccsx_gpu_polish"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_polish_host.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p,
+                                           C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.ccsx_polish_host.restype = C.c_int32
+            L.ccsx_gpu_polish_open.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.ccsx_gpu_polish_close.argtypes = [C.c_void_p]
+            L.ccsx_gpu_polish_close.restype = None
+            L.ccsx_gpu_polish_error.argtypes = [C.c_void_p]
+            L.ccsx_gpu_polish_error.restype = C.c_char_p
+            L.ccsx_gpu_polish.argtypes = [C.c_void_p, C.POINTER(PolishIn), C.c_size_t, C.POINTER(PolishOut),
+                                          C.POINTER(C.c_float)]
+            L.ccsx_gpu_polish_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         L.ccsx_synth_zmw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p,
                                      C.POINTER(C.c_uint32), C.c_char_p]
         L.ccsx_synth_zmw.restype = C.c_uint64
@@ -449,6 +474,47 @@ def map_cigar(m):
     return d
 
 
+POLISH_BAD_MAP = 1
+
+
+def _polish_item(ccs: bytes, segs, maps):
+    """(seqs, seg_off, seg_len, map) arrays of one ZMW for ccsx_polish_in."""
+    lens = _u32([len(x) for x in segs])
+    offs = _u32(np.concatenate([[0], np.cumsum(lens)[:-1]]) if len(segs) else [])
+    if len(maps) != len(segs) or any(len(m) != len(x) for m, x in zip(maps, segs)):
+        raise ValueError("polish: one map word per pushed base, one map per segment")
+    m = _u32(np.concatenate([np.asarray(x, dtype=np.uint32) for x in maps]) if len(maps) else [])
+    return b"".join(segs), offs, lens, m
+
+
+def _split_map(m: np.ndarray, segs) -> list:
+    out, o = [], 0
+    for x in segs:
+        a = m[o:o + len(x)].copy()
+        a.setflags(write=False)
+        out.append(a)
+        o += len(x)
+    return out
+
+
+def polish_host(ccs: bytes, segs, maps):
+    """ccsx_polish_host (SPEC.md §15): the draft ccs, its segments as pushed and
+    their §11 maps -> (seq, qual, (nsub, nins, ndel), [realigned map per
+    segment], status); status POLISH_BAD_MAP gives empty results."""
+    seqs, offs, lens, m = _polish_item(ccs, segs, maps)
+    cap = 2 * len(ccs) + 1
+    oseq = C.create_string_buffer(cap)
+    oqual = (C.c_uint8 * cap)()
+    omap = np.zeros(max(len(m), 1), dtype=np.uint32)
+    counts = (C.c_uint32 * 4)()
+    st = lib().ccsx_polish_host(ccs, len(ccs), seqs, _p32(offs), _p32(lens), len(segs), _p32(m), oseq, oqual, _p32(omap),
+                                counts)
+    if st != 0:
+        return b"", b"", (0, 0, 0), [], int(st)
+    n = counts[0]
+    return oseq.raw[:n], bytes(oqual[:n]), (int(counts[1]), int(counts[2]), int(counts[3])), _split_map(omap, segs), 0
+
+
 def kin_frames(code: int) -> int:
     """ccsx_kin_frames: the frames an 8-bit kinetics code stands for (SPEC.md §13)."""
     return int(lib().ccsx_kin_frames(code))
@@ -653,6 +719,72 @@ class Aligner:
         if self._L.ccsx_gpu_aln_stats(self._ctx, st, 5) != 0:
             self._err("ccsx_gpu_aln_stats")
         return dict(zip(("jobs", "slices", "host_jobs", "rounds", "discarded"), (int(x) for x in st)))
+
+
+class Polisher:
+    """A polisher context on one HIP device (ccsx_gpu_polish_*): SPEC.md §15's
+    realignment of every pushed segment to the draft CCS, the vote and the
+    polished read, for many ZMWs per launch; max_bytes = the most device memory
+    its arena takes (0: the library's default)."""
+
+    def __init__(self, device: int = 0, max_bytes: int = 0):
+        self._L = lib()
+        self._ctx = C.c_void_p()
+        if self._L.ccsx_gpu_polish_open(device, max_bytes, C.byref(self._ctx)) != 0:
+            raise GpuError(f"cannot open a polisher on HIP device {device}")
+        self.kernel_ms = 0.0
+
+    def close(self):
+        if self._ctx:
+            self._L.ccsx_gpu_polish_close(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what: str):
+        raise GpuError(f"{what}: {self._L.ccsx_gpu_polish_error(self._ctx).decode()}")
+
+    def polish(self, items) -> list:
+        """ccsx_gpu_polish on items = [(ccs, segs, maps)]: the draft, its
+        segments as pushed and their §11 maps (Engine.base_map).  Per ZMW
+        (seq, qual, (nsub, nins, ndel), [realigned map per segment], status), as
+        polish_host returns; kernel_ms = the kernels' time."""
+        n = len(items)
+        arr = (PolishIn * max(n, 1))()
+        keep = []
+        for i, (ccs, segs, maps) in enumerate(items):
+            seqs, offs, lens, m = _polish_item(ccs, segs, maps)
+            keep.append((ccs, seqs, offs, lens, m))
+            arr[i].ccs, arr[i].len, arr[i].seqs, arr[i].nseg = ccs, len(ccs), seqs, len(segs)
+            arr[i].seg_off, arr[i].seg_len, arr[i].map = _p32(offs), _p32(lens), _p32(m)
+        out = (PolishOut * max(n, 1))()
+        ms = C.c_float(0)
+        if self._L.ccsx_gpu_polish(self._ctx, arr, n, out, C.byref(ms)) != 0:
+            self._err("ccsx_gpu_polish")
+        self.kernel_ms = float(ms.value)
+        res = []
+        for i, (ccs, segs, maps) in enumerate(items):
+            o = out[i]
+            if o.status != 0:
+                res.append((b"", b"", (0, 0, 0), [], int(o.status)))
+                continue
+            rows = sum(len(x) for x in segs)
+            m = np.ctypeslib.as_array(o.map, (rows,)).copy() if rows else np.zeros(0, np.uint32)
+            res.append((C.string_at(o.seq, o.len), C.string_at(o.qual, o.len), (int(o.nsub), int(o.nins), int(o.ndel)),
+                        _split_map(m, segs), 0))
+        return res
+
+    def stats(self) -> dict:
+        """ccsx_gpu_polish_stats: ZMWs, segments, slices launched, ZMWs run on
+        the host, ZMWs with a bad map."""
+        st = (C.c_uint64 * 5)()
+        if self._L.ccsx_gpu_polish_stats(self._ctx, st, 5) != 0:
+            self._err("ccsx_gpu_polish_stats")
+        return dict(zip(("zmws", "segments", "slices", "host_zmws", "bad_maps"), (int(x) for x in st)))
 
 
 class Engine:

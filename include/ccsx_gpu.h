@@ -440,6 +440,61 @@ const char *ccsx_gpu_aln_error(const ccsx_aln_ctx *ctx);
 int ccsx_gpu_band_align(ccsx_aln_ctx *ctx, const ccsx_band_job *jobs, size_t n, ccsx_pairaln *out, float *kernel_ms);
 int ccsx_gpu_aln_stats(const ccsx_aln_ctx *ctx, uint64_t *stats, uint32_t n);
 
+/* The polisher (SPEC.md §15 on the device, ccsx_polish.hip): every pushed
+ * segment of a ZMW is realigned to its finished draft CCS in a 64-cell band
+ * guided by the segment's §11 map, the realigned bases vote per draft
+ * position, and the polished read is assembled from the votes.  Every result
+ * equals ccsx_polish_host (include/ccsx_host.h) byte for byte.
+ *
+ * ccsx_polish_in: the draft (ccs, len; ASCII), the ZMW's segments as pushed
+ * (seqs + seg_off[k], seg_len[k] bytes, ASCII; after the strand flip) and map
+ * = their §11 words, segments back to back in push order: what
+ * ccsx_gpu_collect and ccsx_gpu_base_map return for a batch that ran with the
+ * base map on.  ccsx_polish_out: the polished read (seq, qual: len bytes each,
+ * qual 0..kQMax, not ASCII), how it differs from the draft (nsub bases changed,
+ * nins inserted, ndel dropped), the realigned map (same layout as the input
+ * map, NULL without one) and status: 0, or CCSX_POLISH_BAD_MAP for a map whose
+ * offsets decrease within a segment or pass the draft's length (no polished
+ * read and no map then; the call's other ZMWs are unaffected).  The pointers
+ * belong to the context and hold until its next ccsx_gpu_polish or its close.
+ *
+ * A polisher context is separate from the consensus contexts and from the
+ * aligner's, as the aligner's is: its own stream and its own device arena of
+ * at most max_bytes (0 = 4 GiB), allocated at the first call and grown as
+ * slices need; a pushed base costs 30 bytes of it and a draft base 49.  The
+ * calls on one context are serialised.  ccsx_gpu_polish: nz ZMWs, cut in order
+ * into slices that fit the arena; a ZMW that no arena of max_bytes holds, or
+ * with a segment or a draft of 2^27 bases or more, runs ccsx_polish_host with
+ * the same result.  kernel_ms (may be NULL) receives the three kernels' time
+ * by HIP events.  Returns 0 or -1.
+ * ccsx_gpu_polish_stats: counters so far, the first min(n, 5) of: [0] ZMWs,
+ * [1] segments, [2] slices launched, [3] ZMWs run on the host, [4] ZMWs with a
+ * bad map. */
+#ifndef CCSX_POLISH_BAD_MAP
+#define CCSX_POLISH_BAD_MAP 1
+#endif
+typedef struct ccsx_polish_ctx ccsx_polish_ctx;
+typedef struct {
+    const char *ccs;
+    uint32_t len;
+    const char *seqs;
+    const uint32_t *seg_off, *seg_len;
+    uint32_t nseg;
+    const uint32_t *map;
+} ccsx_polish_in;
+typedef struct {
+    const char *seq;
+    const uint8_t *qual;
+    uint32_t len, nsub, nins, ndel;
+    const uint32_t *map;
+    int32_t status;
+} ccsx_polish_out;
+int ccsx_gpu_polish_open(int device, uint64_t max_bytes, ccsx_polish_ctx **ctx);
+void ccsx_gpu_polish_close(ccsx_polish_ctx *ctx);
+const char *ccsx_gpu_polish_error(const ccsx_polish_ctx *ctx);
+int ccsx_gpu_polish(ccsx_polish_ctx *ctx, const ccsx_polish_in *z, size_t nz, ccsx_polish_out *out, float *kernel_ms);
+int ccsx_gpu_polish_stats(const ccsx_polish_ctx *ctx, uint64_t *stats, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,19 @@ long ccsx_map_cigar(const uint32_t *map, uint32_t len, ccsx_map_aln *aln, char *
  * discordant site.  -1 also for p == NULL or another strand value. */
 int ccsx_pileup_call(const ccsx_pileup *p, int strand);
 
+/* The polish step of one ZMW as a sequential loop (SPEC.md section 15; the
+ * device's ccsx_gpu_polish gives the same bytes and runs this for the ZMWs its
+ * arena cannot hold).  ccs / len = the draft; seqs, seg_off, seg_len, nseg =
+ * the segments as pushed; map = their section 11 words, segments back to back
+ * in push order.  Writes the polished read to out_seq / out_qual (capacity
+ * 2 len + 1 each; qualities 0..kQMax, not ASCII), the realigned map to out_map
+ * (one word per pushed base) and counts[4] = the polished length, nsub, nins,
+ * ndel.  Returns 0, or CCSX_POLISH_BAD_MAP (nothing but counts written, all
+ * zero) for a map whose offsets decrease within a segment or pass len. */
+int32_t ccsx_polish_host(const char *ccs, uint32_t len, const char *seqs, const uint32_t *seg_off,
+                         const uint32_t *seg_len, uint32_t nseg, const uint32_t *map, char *out_seq,
+                         uint8_t *out_qual, uint32_t *out_map, uint32_t *counts);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
