@@ -858,9 +858,9 @@ private:
     }
 };
 
-}  // namespace
-
-std::unique_ptr<ZmwSource> ZmwSource::open(const char *path, bool is_bam, int nthreads)
+// the record reader of an input (path "-" = stdin); *mm = its whole-file
+// mapping, if that is how it is read
+std::unique_ptr<RecordReader> open_records(const char *path, bool is_bam, int nthreads, MmapSource **mm_out)
 {
     const char *e = getenv("CCSX_INGEST_BLOCK");
     const size_t block = e ? (size_t)std::max<long>(1, atol(e)) : (32u << 20);
@@ -906,10 +906,46 @@ std::unique_ptr<ZmwSource> ZmwSource::open(const char *path, bool is_bam, int nt
         }
     }
     src->block = block;
+    *mm_out = mm;
     std::unique_ptr<RecordReader> rr;
     if (is_bam) rr.reset(new BamReader(std::move(src)));
     else rr.reset(new FxReader(std::move(src)));
+    return rr;
+}
+
+class PlainRecords : public FxRecords {
+public:
+    explicit PlainRecords(std::unique_ptr<RecordReader> rr) : rr_(std::move(rr)) {}
+    bool next(std::string &name, std::string &bases) override
+    {
+        Rec r;
+        std::shared_ptr<Block> keep;
+        if (rr_->next(name, r, keep) < 0) return false;
+        bases.clear();
+        append_bases(r, bases);
+        return true;
+    }
+
+private:
+    std::unique_ptr<RecordReader> rr_;
+};
+
+}  // namespace
+
+std::unique_ptr<ZmwSource> ZmwSource::open(const char *path, bool is_bam, int nthreads)
+{
+    MmapSource *mm = nullptr;
+    auto rr = open_records(path, is_bam, nthreads, &mm);
+    if (!rr) return nullptr;
     return std::unique_ptr<ZmwSource>(new Grouper(std::move(rr), mm));
+}
+
+std::unique_ptr<FxRecords> FxRecords::open(const char *path)
+{
+    MmapSource *mm = nullptr;
+    auto rr = open_records(path, false, 1, &mm);
+    if (!rr) return nullptr;
+    return std::unique_ptr<FxRecords>(new PlainRecords(std::move(rr)));
 }
 
 }  // namespace ccsx_ingest

@@ -77,4 +77,15 @@ public:
     virtual void release(const char *upto) { (void)upto; }
 };
 
+// The records of a FASTA / FASTQ input one by one, with no ZMW grouping and
+// any name (the barcode file of SPEC.md §16): the same sources and the same
+// record parser as ZmwSource's.
+class FxRecords {
+public:
+    static std::unique_ptr<FxRecords> open(const char *path);
+    virtual ~FxRecords() = default;
+    // the next record's name and bases; false at the end of the input
+    virtual bool next(std::string &name, std::string &bases) = 0;
+};
+
 }  // namespace ccsx_ingest

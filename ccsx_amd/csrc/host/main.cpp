@@ -128,6 +128,8 @@ struct Zmw {
     std::string sites;        // -s: the lines of its discordant sites (SPEC.md section 12)
     std::string strands;      // -b: the records of its strand consensuses (SPEC.md section 14)
     std::string polished;     // -p: the record of its polished read (SPEC.md section 15)
+    std::string demux;        // -B -d: the record of its trimmed read, if assigned (SPEC.md section 16)
+    std::string demux_row;    // -B -D: its line of the demultiplexing report
     std::vector<uint8_t> kin;  // -k: the ipd codes of its bases, then the pw codes, parallel to seqs (empty: a subread lacks them)
     std::string kinline;      // -k: its SAM line (SPEC.md section 13)
     bool kin_arrays = false;  // -k: ... carries the four arrays
@@ -179,6 +181,12 @@ int usage()
             "-s     <file>  Strand-discordant sites (tab-separated): per CCS position whose forward and reverse subreads call different bases (or base against gap), the two calls and the per-strand A/C/G/T/gap/ins counts \n"
             "-b     <file>  Per-strand consensus (fasta, fastq with -q): per CCS read the sequence its forward and its reverse subreads support in the alignment the CCS was called from, as <name>/fwd and <name>/rev in the CCS's orientation \n"
             "-p     <file>  Polished reads (fasta, fastq with -q): per CCS read, every subread realigned to the finished CCS on the GPU and the bases voted again per position, as <name>/polished; the main output and the other files stay the draft's \n"
+            "-B     <file>  Barcode FASTA (1..2048 sequences of 1..64 ACGT letters): every CCS read's two ends are scored on the GPU against every barcode in both orientations and the read is assigned to a barcode pair \n"
+            "-d     <file>  With -B: the assigned reads, barcodes clipped (fasta, fastq with -q), the header extended by bc=<name0>--<name1> bs=<score0>,<score1> bx=<clip0>,<clip1> \n"
+            "-D     <file>  With -B: demultiplexing report (tab-separated), one line per CCS read: per end the barcode, orientation, score, runner-up score and clip; the call and why a read is not assigned \n"
+            "-W     <int>   With -B: bases of each read end searched for a barcode, 1..256. [96] \n"
+            "-T     <int>   With -B: an end is called if its score is at least this percentage of the barcode's length. [60] \n"
+            "-L     <int>   With -B: ... and leads the best other barcode's score by at least this. [3] \n"
             "-k     <file>  Consensus kinetics (unaligned SAM; BAM input only): per CCS read its bases, np/fn/rn and, from the subreads' ip/pw tags, the per-strand mean inter-pulse duration and pulse width per base as fi/fp/ri/rp B:C arrays \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
@@ -562,10 +570,14 @@ int main(int argc, char **argv)
     const char *kin_path = nullptr;     // -k
     const char *strand_path = nullptr;  // -b
     const char *polish_path = nullptr;  // -p
+    const char *bc_path = nullptr;      // -B
+    const char *demux_path = nullptr;   // -d
+    const char *bcrep_path = nullptr;   // -D
+    int bc_window = 96, bc_min_pct = 60, bc_min_lead = 3;  // -W -T -L
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -578,6 +590,12 @@ int main(int argc, char **argv)
         case 'k': kin_path = optarg; break;
         case 'b': strand_path = optarg; break;
         case 'p': polish_path = optarg; break;
+        case 'B': bc_path = optarg; break;
+        case 'd': demux_path = optarg; break;
+        case 'D': bcrep_path = optarg; break;
+        case 'W': bc_window = atoi(optarg); break;
+        case 'T': bc_min_pct = atoi(optarg); break;
+        case 'L': bc_min_lead = atoi(optarg); break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -597,6 +615,34 @@ int main(int argc, char **argv)
     if (kin_path && !isbam) {
         fprintf(stderr, "Error! -k needs BAM input (the kinetics are the subreads' ip / pw tags): not with -A\n");
         return 1;
+    }
+    // -B: the barcode set, read and checked before anything else is opened
+    std::vector<std::string> bc_names;
+    std::string bc_seqs;
+    std::vector<uint32_t> bc_off, bc_len;
+    if ((demux_path || bcrep_path) && !bc_path) {
+        fprintf(stderr, "Error! -d and -D need a barcode file (-B)\n");
+        return 1;
+    }
+    if (bc_path) {
+        if (bc_window < 1 || bc_window > 256) {
+            fprintf(stderr, "Error! -W=[%d] (1..256) !\n", bc_window);
+            return 1;
+        }
+        ccsx_barcode_set *bs = ccsx_barcode_read(bc_path);
+        const char *const *nm = nullptr, *const *sq = nullptr;
+        const uint32_t nb = ccsx_barcode_set_get(bs, &nm, &sq);
+        for (uint32_t b = 0; b < nb; ++b) {
+            bc_names.push_back(nm[b]);
+            bc_off.push_back((uint32_t)bc_seqs.size());
+            bc_len.push_back((uint32_t)strlen(sq[b]));
+            bc_seqs += sq[b];
+        }
+        ccsx_barcode_set_free(bs);
+        if (!nb || ccsx_barcode_check(bc_seqs.data(), bc_off.data(), bc_len.data(), nb) != 0) {
+            fprintf(stderr, "Error! %s is not a barcode file: 1..2048 records of 1..64 ACGT letters\n", bc_path);
+            return 1;
+        }
     }
     // main.c:802-826
     const char *in_path = "-";
@@ -654,6 +700,14 @@ int main(int argc, char **argv)
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
+    FILE *fp_dmx = demux_path ? fopen(demux_path, "w") : nullptr;
+    FILE *fp_bcr = bcrep_path ? fopen(bcrep_path, "w") : nullptr;
+    if ((demux_path && !fp_dmx) || (bcrep_path && !fp_bcr)) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    if (fp_bcr)
+        fprintf(fp_bcr, "#name\tlen\tbc0\tstrand0\tscore0\tsecond0\tend0\tbc1\tstrand1\tscore1\tsecond1\tend1\tcl\tcr\tcalled0\tcalled1\tassigned\treason\n");
     if (fp_kin) fprintf(fp_kin, "@HD\tVN:1.6\tSO:unknown\n");
     if (fp_rep) fprintf(fp_rep, "#name\tpass\tsbeg\tslen\tmatch\tmismatch\tins\tdel\tcbeg\tcend\tidentity\n");
     // step 1 pipelined per context (ccsx_gpu_submit / ccsx_gpu_collect: the
@@ -711,6 +765,8 @@ int main(int argc, char **argv)
     // its next call, so a worker keeps pol_m from its call until it has copied them
     ccsx_polish_ctx *pol = nullptr;
     std::mutex pol_m;
+    // -B: the one demultiplexer context, on the first GPU (its calls copy their results out)
+    ccsx_bc_ctx *bc = nullptr;
     bool aln_tried = false;
     const auto tstart = std::chrono::steady_clock::now();
     auto now_ms = [tstart]() {
@@ -965,6 +1021,67 @@ int main(int argc, char **argv)
                     }
                 }
             }
+            if (bc && !qfail) {
+                // -B: the batch's CCS reads are scored here; then the call, the trimmed record and the report line
+                std::vector<ccsx_bc_in> bin;
+                std::vector<size_t> who;
+                for (size_t i = 0; i < f.b.idx.size(); ++i) {
+                    const Zmw &z = ch.zs[f.b.idx[i]];
+                    if (f.out[i].status || z.ccs.empty()) continue;
+                    bin.push_back(ccsx_bc_in{z.ccs.data(), (uint32_t)z.ccs.size()});
+                    who.push_back(f.b.idx[i]);
+                }
+                std::vector<ccsx_bc_out> bo(bin.size());
+                if (!bin.empty() && ccsx_gpu_bc_score(bc, bin.data(), bin.size(), bo.data(), nullptr) != 0) {
+                    std::lock_guard<std::mutex> g2(err_m);
+                    fprintf(stderr, "[ccsx] demultiplexer: %s\n", ccsx_gpu_bc_error(bc));
+                    qfail = true;
+                }
+                static const char *const why[] = {"ok", "end0", "end1", "ends", "insert"};
+                for (size_t i = 0; i < bin.size() && !qfail; ++i) {
+                    Zmw &z = ch.zs[who[i]];
+                    const uint32_t n = (uint32_t)z.ccs.size();
+                    ccsx_bc_call call;
+                    ccsx_barcode_call(&bo[i], bc_len.data(), (uint32_t)bc_len.size(), n, bc_min_pct, bc_min_lead, &call);
+                    const ccsx_bc_end *e = bo[i].e;
+                    char num[160];
+                    if (fp_bcr) {
+                        std::string &s = z.demux_row;
+                        snprintf(num, sizeof num, "/ccs\t%u", n);
+                        s = z.movie + "/" + z.hole + num;
+                        for (int k = 0; k < 2; ++k) {
+                            s += '\t' + bc_names[(size_t)e[k].pattern >> 1];
+                            const char o = (e[k].pattern & 1) ? '-' : '+';
+                            if (e[k].second_pattern < 0) snprintf(num, sizeof num, "\t%c\t%d\t.\t%d", o, e[k].score, e[k].end);
+                            else snprintf(num, sizeof num, "\t%c\t%d\t%d\t%d", o, e[k].score, e[k].second, e[k].end);
+                            s += num;
+                        }
+                        snprintf(num, sizeof num, "\t%u\t%u\t%d\t%d\t%d\t%s\n", call.cl, call.cr, call.called[0], call.called[1],
+                                 call.assigned, why[call.reason]);
+                        s += num;
+                    }
+                    if (fp_dmx && call.assigned) {
+                        // the read's own header, then the pair, the two scores and the two clips
+                        std::string &s = z.demux;
+                        s += fastq ? '@' : '>';
+                        s += z.movie + "/" + z.hole + "/ccs";
+                        if (fastq) {
+                            snprintf(num, sizeof num, " np=%zu rq=%.6f", z.seg_len.size(), z.rq);
+                            s += num;
+                        }
+                        s += " bc=" + bc_names[(size_t)e[0].pattern >> 1] + "--" + bc_names[(size_t)e[1].pattern >> 1];
+                        snprintf(num, sizeof num, " bs=%d,%d bx=%u,%u\n", e[0].score, e[1].score, call.cl, call.cr);
+                        s += num;
+                        s.append(z.ccs, call.cl, n - call.cl - call.cr);
+                        s += '\n';
+                        if (fastq) {
+                            s += "+\n";
+                            s.append(z.qual, call.cl, n - call.cl - call.cr);
+                            s += '\n';
+                        }
+                    }
+                }
+            }
         }
         if ((qfail || (r != 0 && r != -2)) && !fatal.exchange(true)) {
             std::lock_guard<std::mutex> g(err_m);
@@ -1166,6 +1283,11 @@ int main(int argc, char **argv)
                 die("invalid CCSX_KCFG / CCSX_WG_PER_CU / CCSX_SHRED_READ_CAP / CCSX_MEM_FRAC");
         }
         if (fp_pol && ccsx_gpu_polish_open(0, 0, &pol) != 0) die("cannot open the polisher context");
+        if (bc_path) {
+            if (ccsx_gpu_bc_open(0, 0, &bc) != 0) die("cannot open the demultiplexer context");
+            if (ccsx_gpu_bc_set(bc, bc_seqs.data(), bc_off.data(), bc_len.data(), (uint32_t)bc_len.size(), (uint32_t)bc_window) != 0)
+                die(ccsx_gpu_bc_error(bc));
+        }
         // pipelined: batches of at most ~95 % of a slot (ccsx_gpu_slot_bytes),
         // so a submitted batch always fits one launch
         if (async && ccsx_gpu_slot_bytes(ctx[0], &slot_bytes) != 0) die(ccsx_gpu_error(ctx[0]));
@@ -1233,6 +1355,8 @@ int main(int argc, char **argv)
                     if (fp_site) fwrite(z.sites.data(), 1, z.sites.size(), fp_site);
                     if (fp_str) fwrite(z.strands.data(), 1, z.strands.size(), fp_str);
                     if (fp_pol) fwrite(z.polished.data(), 1, z.polished.size(), fp_pol);
+                    if (fp_dmx) fwrite(z.demux.data(), 1, z.demux.size(), fp_dmx);
+                    if (fp_bcr) fwrite(z.demux_row.data(), 1, z.demux_row.size(), fp_bcr);
                     if (fp_kin) {
                         if (!z.kin_arrays) ++nokin;
                         fwrite(z.kinline.data(), 1, z.kinline.size(), fp_kin);
@@ -1324,6 +1448,8 @@ int main(int argc, char **argv)
         if (fp_kin) werr = (ferror(fp_kin) || fclose(fp_kin) != 0) || werr;
         if (fp_str) werr = (ferror(fp_str) || fclose(fp_str) != 0) || werr;
         if (fp_pol) werr = (ferror(fp_pol) || fclose(fp_pol) != 0) || werr;
+        if (fp_dmx) werr = (ferror(fp_dmx) || fclose(fp_dmx) != 0) || werr;
+        if (fp_bcr) werr = (ferror(fp_bcr) || fclose(fp_bcr) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1360,6 +1486,7 @@ int main(int argc, char **argv)
     for (auto *x : ctx) ccsx_gpu_close(x);
     ccsx_gpu_aln_close(aln);
     ccsx_gpu_polish_close(pol);
+    ccsx_gpu_bc_close(bc);
     reap.push(nullptr);
     reaper.join();
     if (timing) fprintf(stderr, "[ccsx] output done at %.0f ms, contexts closed at %.0f ms\n", tw, now_ms());
@@ -1372,6 +1499,8 @@ int main(int argc, char **argv)
     if (fp_kin) (void)fclose(fp_kin);
     if (fp_str) (void)fclose(fp_str);
     if (fp_pol) (void)fclose(fp_pol);
+    if (fp_dmx) (void)fclose(fp_dmx);
+    if (fp_bcr) (void)fclose(fp_bcr);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

@@ -36,11 +36,15 @@ EXPORTS = {
                    "ccsx_gpu_aln_open", "ccsx_gpu_aln_close", "ccsx_gpu_aln_error", "ccsx_gpu_band_align",
                    "ccsx_gpu_aln_stats",
                    "ccsx_gpu_polish_open", "ccsx_gpu_polish_close", "ccsx_gpu_polish_error", "ccsx_gpu_polish",
-                   "ccsx_gpu_polish_stats"],
+                   "ccsx_gpu_polish_stats",
+                   "ccsx_gpu_bc_open", "ccsx_gpu_bc_close", "ccsx_gpu_bc_error", "ccsx_gpu_bc_set", "ccsx_gpu_bc_score",
+                   "ccsx_gpu_bc_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
                     "ccsx_map_cigar", "ccsx_pileup_call", "ccsx_polish_host",
+                    "ccsx_barcode_check", "ccsx_barcode_host", "ccsx_barcode_call", "ccsx_barcode_read",
+                    "ccsx_barcode_set_get", "ccsx_barcode_set_free",
                     "ccsx_prepare_apply_kin", "ccsx_kin_frames", "ccsx_kin_code", "ccsx_kinetics_tags",
                     "ccsx_synth_batch_kinetics",
                     "ccsx_pairwise_seed", "ccsx_pairwise_band", "ccsx_prep_begin", "ccsx_prep_pending",
@@ -80,6 +84,20 @@ class PolishIn(C.Structure):
 class PolishOut(C.Structure):
     _fields_ = [("seq", C.c_void_p), ("qual", C.c_void_p), ("len", C.c_uint32), ("nsub", C.c_uint32),
                 ("nins", C.c_uint32), ("ndel", C.c_uint32), ("map", C.POINTER(C.c_uint32)), ("status", C.c_int32)]
+
+
+class BcIn(C.Structure):
+    _fields_ = [("ccs", C.c_char_p), ("len", C.c_uint32)]
+
+
+class BcOut(C.Structure):
+    # e[2] x (pattern, score, end, second, second_pattern)
+    _fields_ = [("v", C.c_int32 * 10)]
+
+
+class BcCall(C.Structure):
+    _fields_ = [("cl", C.c_uint32), ("cr", C.c_uint32), ("called", C.c_uint8 * 2), ("assigned", C.c_uint8),
+                ("reason", C.c_uint8)]
 
 
 class BatchInfo(C.Structure):
@@ -233,6 +251,29 @@ def lib() -> C.CDLL:
             L.ccsx_gpu_polish.argtypes = [C.c_void_p, C.POINTER(PolishIn), C.c_size_t, C.POINTER(PolishOut),
                                           C.POINTER(C.c_float)]
             L.ccsx_gpu_polish_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
+        if hasattr(L, "ccsx_gpu_bc_score"):  # (absent from the older builds used in A/B runs)
+            bset = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
+            L.ccsx_barcode_check.argtypes = bset
+            L.ccsx_barcode_check.restype = C.c_int32
+            L.ccsx_barcode_host.argtypes = bset + [C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(BcOut)]
+            L.ccsx_barcode_host.restype = C.c_int32
+            L.ccsx_barcode_call.argtypes = [C.POINTER(BcOut), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int32,
+                                            C.c_int32, C.POINTER(BcCall)]
+            L.ccsx_barcode_call.restype = None
+            L.ccsx_barcode_read.argtypes = [C.c_char_p]
+            L.ccsx_barcode_read.restype = C.c_void_p
+            L.ccsx_barcode_set_get.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_char_p))]
+            L.ccsx_barcode_set_get.restype = C.c_uint32
+            L.ccsx_barcode_set_free.argtypes = [C.c_void_p]
+            L.ccsx_barcode_set_free.restype = None
+            L.ccsx_gpu_bc_open.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.ccsx_gpu_bc_close.argtypes = [C.c_void_p]
+            L.ccsx_gpu_bc_close.restype = None
+            L.ccsx_gpu_bc_error.argtypes = [C.c_void_p]
+            L.ccsx_gpu_bc_error.restype = C.c_char_p
+            L.ccsx_gpu_bc_set.argtypes = [C.c_void_p] + bset + [C.c_uint32]
+            L.ccsx_gpu_bc_score.argtypes = [C.c_void_p, C.POINTER(BcIn), C.c_size_t, C.POINTER(BcOut), C.POINTER(C.c_float)]
+            L.ccsx_gpu_bc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         L.ccsx_synth_zmw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p,
                                      C.POINTER(C.c_uint32), C.c_char_p]
         L.ccsx_synth_zmw.restype = C.c_uint64
@@ -719,6 +760,123 @@ class Aligner:
         if self._L.ccsx_gpu_aln_stats(self._ctx, st, 5) != 0:
             self._err("ccsx_gpu_aln_stats")
         return dict(zip(("jobs", "slices", "host_jobs", "rounds", "discarded"), (int(x) for x in st)))
+
+
+BC_NONE = -(1 << 31)  # CCSX_BC_NONE: `second` of a set of one barcode
+BC_REASONS = ("ok", "end0", "end1", "ends", "insert")  # ccsx_bc_call's reason (CCSX_BC_OK ...), as the -D file names it
+
+
+def _barcode_set(barcodes):
+    """(seqs, off, len) arrays of a barcode list for the C-ABI."""
+    bs = [bytes(b) for b in barcodes]
+    lens = _u32([len(b) for b in bs])
+    offs = _u32(np.concatenate([[0], np.cumsum(lens)[:-1]])) if len(bs) else _u32([])
+    return b"".join(bs), offs, lens
+
+
+def _bc_ends(o: BcOut):
+    v = [int(x) for x in o.v]
+    return tuple(v[:5]), tuple(v[5:])
+
+
+def barcode_host(barcodes, ccs: bytes, window: int = 96):
+    """ccsx_barcode_host (SPEC.md §16): per end (pattern, score, end, second,
+    second_pattern) of one CCS read; ValueError for a bad set or window."""
+    seqs, offs, lens = _barcode_set(barcodes)
+    out = BcOut()
+    if lib().ccsx_barcode_host(seqs, _p32(offs), _p32(lens), len(lens), window, ccs, len(ccs), C.byref(out)) != 0:
+        raise ValueError("not a barcode set (1..2048 sequences of 1..64 ACGT letters) or window outside 1..256")
+    return _bc_ends(out)
+
+
+def barcode_call(result, lens, n: int, T: int = 60, D: int = 3):
+    """ccsx_barcode_call: from a read's result (the two ends' five values), the
+    barcodes' lengths and the read's length: (cl, cr, (called0, called1),
+    assigned, reason); reason indexes BC_REASONS."""
+    o = BcOut()
+    for k, x in enumerate(tuple(result[0]) + tuple(result[1])):
+        o.v[k] = x
+    ln = _u32(lens)
+    call = BcCall()
+    lib().ccsx_barcode_call(C.byref(o), _p32(ln), len(ln), n, T, D, C.byref(call))
+    return int(call.cl), int(call.cr), (bool(call.called[0]), bool(call.called[1])), bool(call.assigned), int(call.reason)
+
+
+def read_barcodes(path: str) -> list:
+    """ccsx_barcode_read: [(name, sequence)] of a barcode FASTA, unchecked;
+    OSError if it cannot be opened or holds no record."""
+    L = lib()
+    s = L.ccsx_barcode_read(os.fsencode(path))
+    if not s:
+        raise OSError(f"{path}: cannot open, or no record")
+    try:
+        names, seqs = C.POINTER(C.c_char_p)(), C.POINTER(C.c_char_p)()
+        n = L.ccsx_barcode_set_get(s, C.byref(names), C.byref(seqs))
+        return [(names[i].decode(), bytes(seqs[i])) for i in range(n)]
+    finally:
+        L.ccsx_barcode_set_free(s)
+
+
+class Demux:
+    """A demultiplexer context on one HIP device (ccsx_gpu_bc_*): SPEC.md §16's
+    scores of every barcode pattern against both end windows of many CCS reads
+    per launch; max_bytes = the most device memory its arena takes (0: the
+    library's default)."""
+
+    def __init__(self, device: int = 0, max_bytes: int = 0):
+        self._L = lib()
+        self._ctx = C.c_void_p()
+        if self._L.ccsx_gpu_bc_open(device, max_bytes, C.byref(self._ctx)) != 0:
+            raise GpuError(f"cannot open a demultiplexer on HIP device {device}")
+        self.kernel_ms = 0.0
+
+    def close(self):
+        if self._ctx:
+            self._L.ccsx_gpu_bc_close(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what: str):
+        raise GpuError(f"{what}: {self._L.ccsx_gpu_bc_error(self._ctx).decode()}")
+
+    def set(self, barcodes, window: int = 96) -> None:
+        """ccsx_gpu_bc_set: the set and window of the calls that follow;
+        ValueError for a bad one (the earlier set stays)."""
+        seqs, offs, lens = _barcode_set(barcodes)
+        if not 0 <= window < 1 << 32:
+            raise ValueError("window outside 1..256")
+        if self._L.ccsx_gpu_bc_set(self._ctx, seqs, _p32(offs), _p32(lens), len(lens), window) != 0:
+            if self._L.ccsx_barcode_check(seqs, _p32(offs), _p32(lens), len(lens)) != 0 or not 1 <= window <= 256:
+                raise ValueError("not a barcode set (1..2048 sequences of 1..64 ACGT letters) or window outside 1..256")
+            self._err("ccsx_gpu_bc_set")
+
+    def score(self, reads) -> list:
+        """ccsx_gpu_bc_score on a list of CCS reads: per read the two ends'
+        (pattern, score, end, second, second_pattern), as barcode_host
+        returns; kernel_ms = the kernel's time."""
+        n = len(reads)
+        arr = (BcIn * max(n, 1))()
+        keep = [bytes(r) for r in reads]
+        for i, r in enumerate(keep):
+            arr[i].ccs, arr[i].len = r, len(r)
+        out = (BcOut * max(n, 1))()
+        ms = C.c_float(0)
+        if self._L.ccsx_gpu_bc_score(self._ctx, arr, n, out, C.byref(ms)) != 0:
+            self._err("ccsx_gpu_bc_score")
+        self.kernel_ms = float(ms.value)
+        return [_bc_ends(out[i]) for i in range(n)]
+
+    def stats(self) -> dict:
+        """ccsx_gpu_bc_stats: reads scored, slices launched, sets."""
+        st = (C.c_uint64 * 3)()
+        if self._L.ccsx_gpu_bc_stats(self._ctx, st, 3) != 0:
+            self._err("ccsx_gpu_bc_stats")
+        return dict(zip(("zmws", "slices", "sets"), (int(x) for x in st)))
 
 
 class Polisher:

@@ -495,6 +495,58 @@ const char *ccsx_gpu_polish_error(const ccsx_polish_ctx *ctx);
 int ccsx_gpu_polish(ccsx_polish_ctx *ctx, const ccsx_polish_in *z, size_t nz, ccsx_polish_out *out, float *kernel_ms);
 int ccsx_gpu_polish_stats(const ccsx_polish_ctx *ctx, uint64_t *stats, uint32_t n);
 
+/* The demultiplexer (SPEC.md §16 on the device, ccsx_barcode.hip): every
+ * barcode of a set, as given and reverse-complemented, is aligned to both end
+ * windows of every CCS read (pattern global, start in the window free, +1 / -2
+ * / -2), and per (read, end) the best pattern, its score and end column and
+ * the best pattern of another barcode come back.  Every result equals
+ * ccsx_barcode_host (include/ccsx_host.h) field for field; ccsx_barcode_call
+ * (there) turns a result into the call and the clip lengths.
+ *
+ * ccsx_bc_in: one CCS read (ASCII; len may be 0).  ccsx_bc_out: e[0] for the
+ * window at the read's start, e[1] for the window at the start of its reverse
+ * complement, so both are read from the outside inwards: pattern = 2 b + o
+ * (barcode b of the set; o = 1: its reverse complement), score, end = the first
+ * window column that reaches the score (the clip length at that end), second =
+ * the largest score of a pattern of another barcode and second_pattern = the
+ * smallest such pattern (CCSX_BC_NONE and -1 for a set of one barcode).
+ *
+ * A demultiplexer context is separate from the consensus contexts, the
+ * aligner's and the polisher's: its own stream, the current set's pattern table
+ * (at most 128 KiB) and its own device arena of at most max_bytes (0 = 64 MiB;
+ * never less than 1 KiB, one read's share at the widest window), allocated at
+ * the first call and grown as slices need; a read costs 2 Wn + 44 bytes of it.
+ * The calls on one context are serialised.
+ * ccsx_gpu_bc_set: the set for the calls that follow: B sequences (seqs +
+ * off[b], len[b] letters ACGT in either case), 1 <= B <= 2048, 1 <= len <= 64,
+ * and the window length 1 <= Wn <= 256.  Returns -1, the earlier set kept, for
+ * anything else.  Nothing of an earlier set survives a new one.
+ * ccsx_gpu_bc_score: nz reads, cut in order into slices that fit the arena;
+ * out receives nz results.  kernel_ms (may be NULL) receives the kernel's time
+ * by HIP events.  Returns 0, or -1 (also without a set).
+ * ccsx_gpu_bc_stats: counters so far, the first min(n, 3) of: [0] reads,
+ * [1] slices launched, [2] sets. */
+#ifndef CCSX_BC_NONE
+#define CCSX_BC_NONE INT32_MIN
+#endif
+typedef struct ccsx_bc_ctx ccsx_bc_ctx;
+typedef struct {
+    const char *ccs;
+    uint32_t len;
+} ccsx_bc_in;
+typedef struct {
+    int32_t pattern, score, end, second, second_pattern;
+} ccsx_bc_end;
+typedef struct {
+    ccsx_bc_end e[2];
+} ccsx_bc_out;
+int ccsx_gpu_bc_open(int device, uint64_t max_bytes, ccsx_bc_ctx **ctx);
+void ccsx_gpu_bc_close(ccsx_bc_ctx *ctx);
+const char *ccsx_gpu_bc_error(const ccsx_bc_ctx *ctx);
+int ccsx_gpu_bc_set(ccsx_bc_ctx *ctx, const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t B, uint32_t Wn);
+int ccsx_gpu_bc_score(ccsx_bc_ctx *ctx, const ccsx_bc_in *z, size_t nz, ccsx_bc_out *out, float *kernel_ms);
+int ccsx_gpu_bc_stats(const ccsx_bc_ctx *ctx, uint64_t *stats, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,41 @@ int32_t ccsx_polish_host(const char *ccs, uint32_t len, const char *seqs, const 
                          const uint32_t *seg_len, uint32_t nseg, const uint32_t *map, char *out_seq,
                          uint8_t *out_qual, uint32_t *out_map, uint32_t *counts);
 
+/* Barcode demultiplexing of CCS reads (SPEC.md section 16; the device's
+ * ccsx_gpu_bc_score gives the same values).
+ * ccsx_barcode_check: 0 for a barcode set (1 <= B <= 2048 sequences seqs +
+ * off[b] of 1 <= len[b] <= 64 letters ACGT in either case), else -1.
+ * ccsx_barcode_host: the definition as a sequential loop, for one read ccs /
+ * n (ASCII; n may be 0) and the window length Wn; writes out (ccsx_bc_out,
+ * include/ccsx_gpu.h).  Returns 0, or -1 (out untouched) for a bad set or a Wn
+ * outside 1 .. 256.
+ * ccsx_barcode_call: the call of one read of n bases from its result r: end e
+ * is called iff 100 x score >= T x L (L = the length of the winning pattern's
+ * barcode, from len) and (B = 1 or score - second >= D); cl / cr = the clip
+ * length (r's end) of end 0 / 1 if called, else 0; the read is assigned iff
+ * both ends are called and cl + cr < n, and its trimmed read is then
+ * ccs[cl, n - cr).  reason: CCSX_BC_OK, or why it is not assigned. */
+enum { CCSX_BC_OK = 0, CCSX_BC_NO_END0 = 1, CCSX_BC_NO_END1 = 2, CCSX_BC_NO_ENDS = 3, CCSX_BC_NO_INSERT = 4 };
+typedef struct {
+    uint32_t cl, cr;
+    uint8_t called[2], assigned, reason;
+} ccsx_bc_call;
+int32_t ccsx_barcode_check(const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t B);
+int32_t ccsx_barcode_host(const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t B, uint32_t Wn,
+                          const char *ccs, uint32_t n, ccsx_bc_out *out);
+void ccsx_barcode_call(const ccsx_bc_out *r, const uint32_t *len, uint32_t B, uint32_t n, int32_t T, int32_t D,
+                       ccsx_bc_call *call);
+/* A barcode FASTA (or FASTQ; gzip allowed), read with the subread reader's
+ * record parser: a record's name is its header up to the first white space.
+ * ccsx_barcode_read returns NULL if the file cannot be opened or holds no
+ * record; the set is then checked with ccsx_barcode_set_get + ccsx_barcode_check.
+ * ccsx_barcode_set_get: the number of records; names / seqs (each may be
+ * NULL) receive arrays of that many NUL-terminated strings, owned by the set. */
+typedef struct ccsx_barcode_set ccsx_barcode_set;
+ccsx_barcode_set *ccsx_barcode_read(const char *path);
+uint32_t ccsx_barcode_set_get(const ccsx_barcode_set *s, const char *const **names, const char *const **seqs);
+void ccsx_barcode_set_free(ccsx_barcode_set *s);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
