@@ -130,6 +130,8 @@ struct Zmw {
     std::string polished;     // -p: the record of its polished read (SPEC.md section 15)
     std::string demux;        // -B -d: the record of its trimmed read, if assigned (SPEC.md section 16)
     std::string demux_row;    // -B -D: its line of the demultiplexing report
+    std::string scan_rows;    // -I -i: the lines of its adapter hits (SPEC.md section 17)
+    std::string pieces;       // -I -S: the records of its pieces
     std::vector<uint8_t> kin;  // -k: the ipd codes of its bases, then the pw codes, parallel to seqs (empty: a subread lacks them)
     std::string kinline;      // -k: its SAM line (SPEC.md section 13)
     bool kin_arrays = false;  // -k: ... carries the four arrays
@@ -187,6 +189,11 @@ int usage()
             "-W     <int>   With -B: bases of each read end searched for a barcode, 1..256. [96] \n"
             "-T     <int>   With -B: an end is called if its score is at least this percentage of the barcode's length. [60] \n"
             "-L     <int>   With -B: ... and leads the best other barcode's score by at least this. [3] \n"
+            "-I     <file>  Adapter FASTA (1..64 sequences of 1..64 ACGT letters): every CCS read is scanned on the GPU, along its whole length, for every adapter in both orientations \n"
+            "-i     <file>  With -I: adapter hit report (tab-separated), one line per hit: the read, its length, the adapter, orientation, start, end, score and the adapter's length \n"
+            "-S     <file>  With -I: the reads cut at their hits (fasta, fastq with -q): the pieces as <name>/<b>_<e> la=<adapter><+|-> ra=<adapter><+|-> (. at a read's end) \n"
+            "-E     <int>   With -I: a place is a hit if its score is at least this percentage of the adapter's length, 1..100. [75] \n"
+            "-e     <int>   With -I: the shortest piece -S writes. [50] \n"
             "-k     <file>  Consensus kinetics (unaligned SAM; BAM input only): per CCS read its bases, np/fn/rn and, from the subreads' ip/pw tags, the per-strand mean inter-pulse duration and pulse width per base as fi/fp/ri/rp B:C arrays \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
@@ -574,10 +581,15 @@ int main(int argc, char **argv)
     const char *demux_path = nullptr;   // -d
     const char *bcrep_path = nullptr;   // -D
     int bc_window = 96, bc_min_pct = 60, bc_min_lead = 3;  // -W -T -L
+    const char *ad_path = nullptr;      // -I
+    const char *hit_path = nullptr;     // -i
+    const char *piece_path = nullptr;   // -S
+    int ad_min_pct = 75, ad_min_piece = 50;  // -E -e
+    bool ad_opts = false;               // -E or -e given
     std::unordered_set<std::string> hole_set;
     std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
     bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:I:i:S:E:e:")) != -1) {
         switch (c) {
         case 'm': min_subread_len = atoi(optarg); break;
         case 'M': max_subread_len = atoi(optarg); break;
@@ -596,6 +608,11 @@ int main(int argc, char **argv)
         case 'W': bc_window = atoi(optarg); break;
         case 'T': bc_min_pct = atoi(optarg); break;
         case 'L': bc_min_lead = atoi(optarg); break;
+        case 'I': ad_path = optarg; break;
+        case 'i': hit_path = optarg; break;
+        case 'S': piece_path = optarg; break;
+        case 'E': ad_min_pct = atoi(optarg), ad_opts = true; break;
+        case 'e': ad_min_piece = atoi(optarg), ad_opts = true; break;
         case 'X':  // main.c:772-782
             have_holes = true;
             hole_set = exclude_holes(xbuf, optarg);
@@ -641,6 +658,38 @@ int main(int argc, char **argv)
         ccsx_barcode_set_free(bs);
         if (!nb || ccsx_barcode_check(bc_seqs.data(), bc_off.data(), bc_len.data(), nb) != 0) {
             fprintf(stderr, "Error! %s is not a barcode file: 1..2048 records of 1..64 ACGT letters\n", bc_path);
+            return 1;
+        }
+    }
+    // -I: the adapter set, read and checked before anything else is opened
+    std::vector<std::string> ad_names;
+    std::string ad_seqs;
+    std::vector<uint32_t> ad_off, ad_len;
+    if ((hit_path || piece_path || ad_opts) && !ad_path) {
+        fprintf(stderr, "Error! -i, -S, -E and -e need an adapter file (-I)\n");
+        return 1;
+    }
+    if (ad_path) {
+        if (ad_min_pct < 1 || ad_min_pct > 100) {
+            fprintf(stderr, "Error! -E=[%d] (1..100) !\n", ad_min_pct);
+            return 1;
+        }
+        if (ad_min_piece < 0) {
+            fprintf(stderr, "Error! -e=[%d] (>=0) !\n", ad_min_piece);
+            return 1;
+        }
+        ccsx_barcode_set *as = ccsx_barcode_read(ad_path);
+        const char *const *nm = nullptr, *const *sq = nullptr;
+        const uint32_t na = ccsx_barcode_set_get(as, &nm, &sq);
+        for (uint32_t a = 0; a < na; ++a) {
+            ad_names.push_back(nm[a]);
+            ad_off.push_back((uint32_t)ad_seqs.size());
+            ad_len.push_back((uint32_t)strlen(sq[a]));
+            ad_seqs += sq[a];
+        }
+        ccsx_barcode_set_free(as);
+        if (!na || ccsx_scan_check(ad_seqs.data(), ad_off.data(), ad_len.data(), na, (uint32_t)ad_min_pct) != 0) {
+            fprintf(stderr, "Error! %s is not an adapter file: 1..64 records of 1..64 ACGT letters\n", ad_path);
             return 1;
         }
     }
@@ -706,6 +755,13 @@ int main(int argc, char **argv)
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
+    FILE *fp_hit = hit_path ? fopen(hit_path, "w") : nullptr;
+    FILE *fp_pcs = piece_path ? fopen(piece_path, "w") : nullptr;
+    if ((hit_path && !fp_hit) || (piece_path && !fp_pcs)) {
+        fprintf(stderr, "Cannot open file for write!\n");
+        return 1;
+    }
+    if (fp_hit) fprintf(fp_hit, "#name\tlen\tadapter\tstrand\tstart\tend\tscore\talen\n");
     if (fp_bcr)
         fprintf(fp_bcr, "#name\tlen\tbc0\tstrand0\tscore0\tsecond0\tend0\tbc1\tstrand1\tscore1\tsecond1\tend1\tcl\tcr\tcalled0\tcalled1\tassigned\treason\n");
     if (fp_kin) fprintf(fp_kin, "@HD\tVN:1.6\tSO:unknown\n");
@@ -767,6 +823,10 @@ int main(int argc, char **argv)
     std::mutex pol_m;
     // -B: the one demultiplexer context, on the first GPU (its calls copy their results out)
     ccsx_bc_ctx *bc = nullptr;
+    // -I: the one scanner context, on the first GPU; its hits hold until its
+    // next call, so a worker keeps scan_m from its call until it has used them
+    ccsx_scan_ctx *scn = nullptr;
+    std::mutex scan_m;
     bool aln_tried = false;
     const auto tstart = std::chrono::steady_clock::now();
     auto now_ms = [tstart]() {
@@ -1082,6 +1142,65 @@ int main(int argc, char **argv)
                     }
                 }
             }
+            if (scn && !qfail) {
+                // -I: the batch's CCS reads are scanned here; then the report lines and the pieces
+                std::vector<ccsx_scan_in> sin;
+                std::vector<size_t> who;
+                for (size_t i = 0; i < f.b.idx.size(); ++i) {
+                    const Zmw &z = ch.zs[f.b.idx[i]];
+                    if (f.out[i].status || z.ccs.empty()) continue;
+                    sin.push_back(ccsx_scan_in{z.ccs.data(), (uint32_t)z.ccs.size()});
+                    who.push_back(f.b.idx[i]);
+                }
+                std::lock_guard<std::mutex> gs(scan_m);
+                const ccsx_scan_hit *hits = nullptr;
+                uint64_t nhits = 0;
+                if (!sin.empty() && ccsx_gpu_scan(scn, sin.data(), sin.size(), &hits, &nhits, nullptr) != 0) {
+                    std::lock_guard<std::mutex> g2(err_m);
+                    fprintf(stderr, "[ccsx] scanner: %s\n", ccsx_gpu_scan_error(scn));
+                    qfail = true;
+                }
+                std::vector<ccsx_scan_piece> pcs;
+                uint64_t h0 = 0;
+                for (size_t i = 0; i < sin.size() && !qfail; ++i) {
+                    Zmw &z = ch.zs[who[i]];
+                    const uint32_t n = (uint32_t)z.ccs.size();
+                    uint64_t h1 = h0;
+                    while (h1 < nhits && hits[h1].read == i) ++h1;
+                    const ccsx_scan_hit *h = hits + h0;
+                    const uint64_t nh = h1 - h0;
+                    h0 = h1;
+                    char num[160];
+                    const std::string name = z.movie + "/" + z.hole + "/ccs";
+                    if (fp_hit)
+                        for (uint64_t k = 0; k < nh; ++k) {
+                            snprintf(num, sizeof num, "\t%c\t%u\t%u\t%d\t%u\n", h[k].orient ? '-' : '+', h[k].start, h[k].end,
+                                     h[k].score, ad_len[h[k].adapter]);
+                            z.scan_rows += name + '\t' + std::to_string(n) + '\t' + ad_names[h[k].adapter] + num;
+                        }
+                    if (fp_pcs) {
+                        const int64_t np = ccsx_scan_cut(h, nh, n, (uint32_t)ad_min_piece, nullptr, 0);
+                        pcs.resize((size_t)np);
+                        ccsx_scan_cut(h, nh, n, (uint32_t)ad_min_piece, pcs.data(), (uint64_t)np);
+                        auto flank = [&](int32_t k) {
+                            return k < 0 ? std::string(".") : ad_names[h[k].adapter] + (h[k].orient ? '-' : '+');
+                        };
+                        for (const ccsx_scan_piece &p : pcs) {
+                            std::string &s = z.pieces;
+                            snprintf(num, sizeof num, "/%u_%u", p.b, p.e);
+                            s += fastq ? '@' : '>';
+                            s += name + num + " la=" + flank(p.left) + " ra=" + flank(p.right) + '\n';
+                            s.append(z.ccs, p.b, p.e - p.b);
+                            s += '\n';
+                            if (fastq) {
+                                s += "+\n";
+                                s.append(z.qual, p.b, p.e - p.b);
+                                s += '\n';
+                            }
+                        }
+                    }
+                }
+            }
         }
         if ((qfail || (r != 0 && r != -2)) && !fatal.exchange(true)) {
             std::lock_guard<std::mutex> g(err_m);
@@ -1288,6 +1407,11 @@ int main(int argc, char **argv)
             if (ccsx_gpu_bc_set(bc, bc_seqs.data(), bc_off.data(), bc_len.data(), (uint32_t)bc_len.size(), (uint32_t)bc_window) != 0)
                 die(ccsx_gpu_bc_error(bc));
         }
+        if (ad_path) {
+            if (ccsx_gpu_scan_open(0, 0, &scn) != 0) die("cannot open the scanner context");
+            if (ccsx_gpu_scan_set(scn, ad_seqs.data(), ad_off.data(), ad_len.data(), (uint32_t)ad_len.size(), (uint32_t)ad_min_pct) != 0)
+                die(ccsx_gpu_scan_error(scn));
+        }
         // pipelined: batches of at most ~95 % of a slot (ccsx_gpu_slot_bytes),
         // so a submitted batch always fits one launch
         if (async && ccsx_gpu_slot_bytes(ctx[0], &slot_bytes) != 0) die(ccsx_gpu_error(ctx[0]));
@@ -1357,6 +1481,8 @@ int main(int argc, char **argv)
                     if (fp_pol) fwrite(z.polished.data(), 1, z.polished.size(), fp_pol);
                     if (fp_dmx) fwrite(z.demux.data(), 1, z.demux.size(), fp_dmx);
                     if (fp_bcr) fwrite(z.demux_row.data(), 1, z.demux_row.size(), fp_bcr);
+                    if (fp_hit) fwrite(z.scan_rows.data(), 1, z.scan_rows.size(), fp_hit);
+                    if (fp_pcs) fwrite(z.pieces.data(), 1, z.pieces.size(), fp_pcs);
                     if (fp_kin) {
                         if (!z.kin_arrays) ++nokin;
                         fwrite(z.kinline.data(), 1, z.kinline.size(), fp_kin);
@@ -1450,6 +1576,8 @@ int main(int argc, char **argv)
         if (fp_pol) werr = (ferror(fp_pol) || fclose(fp_pol) != 0) || werr;
         if (fp_dmx) werr = (ferror(fp_dmx) || fclose(fp_dmx) != 0) || werr;
         if (fp_bcr) werr = (ferror(fp_bcr) || fclose(fp_bcr) != 0) || werr;
+        if (fp_hit) werr = (ferror(fp_hit) || fclose(fp_hit) != 0) || werr;
+        if (fp_pcs) werr = (ferror(fp_pcs) || fclose(fp_pcs) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1487,6 +1615,7 @@ int main(int argc, char **argv)
     ccsx_gpu_aln_close(aln);
     ccsx_gpu_polish_close(pol);
     ccsx_gpu_bc_close(bc);
+    ccsx_gpu_scan_close(scn);
     reap.push(nullptr);
     reaper.join();
     if (timing) fprintf(stderr, "[ccsx] output done at %.0f ms, contexts closed at %.0f ms\n", tw, now_ms());
@@ -1501,6 +1630,8 @@ int main(int argc, char **argv)
     if (fp_pol) (void)fclose(fp_pol);
     if (fp_dmx) (void)fclose(fp_dmx);
     if (fp_bcr) (void)fclose(fp_bcr);
+    if (fp_hit) (void)fclose(fp_hit);
+    if (fp_pcs) (void)fclose(fp_pcs);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }

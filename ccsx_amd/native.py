@@ -38,13 +38,16 @@ EXPORTS = {
                    "ccsx_gpu_polish_open", "ccsx_gpu_polish_close", "ccsx_gpu_polish_error", "ccsx_gpu_polish",
                    "ccsx_gpu_polish_stats",
                    "ccsx_gpu_bc_open", "ccsx_gpu_bc_close", "ccsx_gpu_bc_error", "ccsx_gpu_bc_set", "ccsx_gpu_bc_score",
-                   "ccsx_gpu_bc_stats"],
+                   "ccsx_gpu_bc_stats",
+                   "ccsx_gpu_scan_open", "ccsx_gpu_scan_close", "ccsx_gpu_scan_error", "ccsx_gpu_scan_set", "ccsx_gpu_scan",
+                   "ccsx_gpu_scan_tracks", "ccsx_gpu_scan_tile", "ccsx_gpu_scan_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
                     "ccsx_map_cigar", "ccsx_pileup_call", "ccsx_polish_host",
                     "ccsx_barcode_check", "ccsx_barcode_host", "ccsx_barcode_call", "ccsx_barcode_read",
                     "ccsx_barcode_set_get", "ccsx_barcode_set_free",
+                    "ccsx_scan_check", "ccsx_scan_host", "ccsx_scan_start", "ccsx_scan_cut",
                     "ccsx_prepare_apply_kin", "ccsx_kin_frames", "ccsx_kin_code", "ccsx_kinetics_tags",
                     "ccsx_synth_batch_kinetics",
                     "ccsx_pairwise_seed", "ccsx_pairwise_band", "ccsx_prep_begin", "ccsx_prep_pending",
@@ -98,6 +101,15 @@ class BcOut(C.Structure):
 class BcCall(C.Structure):
     _fields_ = [("cl", C.c_uint32), ("cr", C.c_uint32), ("called", C.c_uint8 * 2), ("assigned", C.c_uint8),
                 ("reason", C.c_uint8)]
+
+
+class ScanHit(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("adapter", C.c_uint32), ("orient", C.c_uint32), ("start", C.c_uint32),
+                ("end", C.c_uint32), ("score", C.c_int32)]
+
+
+class ScanPiece(C.Structure):
+    _fields_ = [("b", C.c_uint32), ("e", C.c_uint32), ("left", C.c_int32), ("right", C.c_int32)]
 
 
 class BatchInfo(C.Structure):
@@ -274,6 +286,28 @@ def lib() -> C.CDLL:
             L.ccsx_gpu_bc_set.argtypes = [C.c_void_p] + bset + [C.c_uint32]
             L.ccsx_gpu_bc_score.argtypes = [C.c_void_p, C.POINTER(BcIn), C.c_size_t, C.POINTER(BcOut), C.POINTER(C.c_float)]
             L.ccsx_gpu_bc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
+        if hasattr(L, "ccsx_gpu_scan"):  # (absent from the older builds used in A/B runs)
+            aset = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]
+            L.ccsx_scan_check.argtypes = aset
+            L.ccsx_scan_check.restype = C.c_int32
+            L.ccsx_scan_host.argtypes = aset + [C.c_char_p, C.c_uint32, C.POINTER(ScanHit), C.c_uint64]
+            L.ccsx_scan_host.restype = C.c_int64
+            L.ccsx_scan_start.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32,
+                                          C.POINTER(C.c_int32)]
+            L.ccsx_scan_start.restype = C.c_int32
+            L.ccsx_scan_cut.argtypes = [C.POINTER(ScanHit), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(ScanPiece), C.c_uint64]
+            L.ccsx_scan_cut.restype = C.c_int64
+            L.ccsx_gpu_scan_open.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.ccsx_gpu_scan_close.argtypes = [C.c_void_p]
+            L.ccsx_gpu_scan_close.restype = None
+            L.ccsx_gpu_scan_error.argtypes = [C.c_void_p]
+            L.ccsx_gpu_scan_error.restype = C.c_char_p
+            L.ccsx_gpu_scan_set.argtypes = [C.c_void_p] + aset
+            L.ccsx_gpu_scan.argtypes = [C.c_void_p, C.POINTER(BcIn), C.c_size_t, C.POINTER(C.POINTER(ScanHit)),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+            L.ccsx_gpu_scan_tracks.argtypes = [C.c_void_p, C.POINTER(BcIn), C.c_size_t, C.c_void_p, C.c_uint64]
+            L.ccsx_gpu_scan_tile.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.ccsx_gpu_scan_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         L.ccsx_synth_zmw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p,
                                      C.POINTER(C.c_uint32), C.c_char_p]
         L.ccsx_synth_zmw.restype = C.c_uint64
@@ -877,6 +911,145 @@ class Demux:
         if self._L.ccsx_gpu_bc_stats(self._ctx, st, 3) != 0:
             self._err("ccsx_gpu_bc_stats")
         return dict(zip(("zmws", "slices", "sets"), (int(x) for x in st)))
+
+
+_SCAN_SET_ERR = "not an adapter set (1..64 sequences of 1..64 ACGT letters) or threshold outside 1..100"
+
+
+def _scan_hit(h: ScanHit) -> tuple:
+    return int(h.adapter), int(h.orient), int(h.start), int(h.end), int(h.score)
+
+
+def scan_host(adapters, ccs: bytes, T: int = 75) -> list:
+    """ccsx_scan_host (SPEC.md §17): the hits of one CCS read as (adapter,
+    orient, start, end, score) by (end, adapter); ValueError for a bad set or T."""
+    seqs, offs, lens = _barcode_set(adapters)
+    if not 0 <= T < 1 << 32:
+        raise ValueError(_SCAN_SET_ERR)
+    L = lib()
+    n = L.ccsx_scan_host(seqs, _p32(offs), _p32(lens), len(lens), T, ccs, len(ccs), None, 0)
+    if n < 0:
+        raise ValueError(_SCAN_SET_ERR)
+    hits = (ScanHit * max(n, 1))()
+    if L.ccsx_scan_host(seqs, _p32(offs), _p32(lens), len(lens), T, ccs, len(ccs), hits, n) != n:
+        raise RuntimeError("ccsx_scan_host: the second pass disagrees with the first")
+    return [_scan_hit(hits[i]) for i in range(n)]
+
+
+def scan_start(adapter: bytes, orient: int, ccs: bytes, end: int) -> tuple:
+    """ccsx_scan_start: (start, the anchored maximum) of a hit that ends at
+    column `end`."""
+    sc = C.c_int32(0)
+    s = lib().ccsx_scan_start(bytes(adapter), len(adapter), orient, ccs, len(ccs), end, C.byref(sc))
+    if s < 0:
+        raise ValueError("adapter length outside 1..64 or end past the read")
+    return int(s), int(sc.value)
+
+
+def scan_cut(hits, n: int, lmin: int = 50) -> list:
+    """ccsx_scan_cut: the pieces (b, e, left, right) of a read of n bases from
+    its hits (as scan_host lists them); left / right index the flanking hit,
+    -1 at the read's end."""
+    arr = (ScanHit * max(len(hits), 1))()
+    for k, (a, o, s, e, sc) in enumerate(hits):
+        arr[k].adapter, arr[k].orient, arr[k].start, arr[k].end, arr[k].score = a, o, s, e, sc
+    L = lib()
+    m = L.ccsx_scan_cut(arr, len(hits), n, lmin, None, 0)
+    out = (ScanPiece * max(m, 1))()
+    L.ccsx_scan_cut(arr, len(hits), n, lmin, out, m)
+    return [(int(p.b), int(p.e), int(p.left), int(p.right)) for p in out[:m]]
+
+
+class Scanner:
+    """An adapter scanner context on one HIP device (ccsx_gpu_scan_*): SPEC.md
+    §17's hits of every adapter, in both orientations, along whole CCS reads,
+    many reads per launch; max_bytes = the most device memory its arena takes
+    (0: the library's default)."""
+
+    def __init__(self, device: int = 0, max_bytes: int = 0):
+        self._L = lib()
+        self._ctx = C.c_void_p()
+        if self._L.ccsx_gpu_scan_open(device, max_bytes, C.byref(self._ctx)) != 0:
+            raise GpuError(f"cannot open a scanner on HIP device {device}")
+        self.kernel_ms = 0.0
+        self._npat = 0
+
+    def close(self):
+        if self._ctx:
+            self._L.ccsx_gpu_scan_close(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what: str):
+        raise GpuError(f"{what}: {self._L.ccsx_gpu_scan_error(self._ctx).decode()}")
+
+    @staticmethod
+    def tile(rows: int) -> tuple:
+        """ccsx_gpu_scan_tile: (TC, WU) of the kernel for `rows` rows."""
+        tc, wu = C.c_uint32(0), C.c_uint32(0)
+        if lib().ccsx_gpu_scan_tile(rows, C.byref(tc), C.byref(wu)) != 0:
+            raise ValueError("rows is one of 16, 32, 48, 64")
+        return int(tc.value), int(wu.value)
+
+    def set(self, adapters, T: int = 75) -> None:
+        """ccsx_gpu_scan_set: the set and threshold of the calls that follow;
+        ValueError for a bad one (the earlier set stays)."""
+        seqs, offs, lens = _barcode_set(adapters)
+        if not 0 <= T < 1 << 32:
+            raise ValueError(_SCAN_SET_ERR)
+        if self._L.ccsx_gpu_scan_set(self._ctx, seqs, _p32(offs), _p32(lens), len(lens), T) != 0:
+            if self._L.ccsx_scan_check(seqs, _p32(offs), _p32(lens), len(lens), T) != 0:
+                raise ValueError(_SCAN_SET_ERR)
+            self._err("ccsx_gpu_scan_set")
+        self._npat = 2 * len(lens)
+
+    def _reads(self, reads):
+        keep = [bytes(r) for r in reads]
+        arr = (BcIn * max(len(keep), 1))()
+        for i, r in enumerate(keep):
+            arr[i].ccs, arr[i].len = r, len(r)
+        return keep, arr
+
+    def scan(self, reads) -> list:
+        """ccsx_gpu_scan on a list of CCS reads: per read its hits as
+        scan_host returns them; kernel_ms = the kernels' time."""
+        keep, arr = self._reads(reads)
+        hits, n, ms = C.POINTER(ScanHit)(), C.c_uint64(0), C.c_float(0)
+        if self._L.ccsx_gpu_scan(self._ctx, arr, len(keep), C.byref(hits), C.byref(n), C.byref(ms)) != 0:
+            self._err("ccsx_gpu_scan")
+        self.kernel_ms = float(ms.value)
+        out = [[] for _ in keep]
+        for k in range(n.value):
+            out[hits[k].read].append(_scan_hit(hits[k]))
+        return out
+
+    def tracks(self, reads) -> list:
+        """ccsx_gpu_scan_tracks: per read the bottom rows S_p(j) of the set's
+        patterns as an int8 array of shape (2 A, len + 1)."""
+        keep, arr = self._reads(reads)
+        total = sum(self._npat * (len(r) + 1) for r in keep)
+        buf = np.zeros(max(total, 1), np.int8)
+        if self._L.ccsx_gpu_scan_tracks(self._ctx, arr, len(keep), buf.ctypes.data, total) != 0:
+            self._err("ccsx_gpu_scan_tracks")
+        out, at = [], 0
+        for r in keep:
+            sz = self._npat * (len(r) + 1)
+            out.append(buf[at:at + sz].reshape(self._npat, len(r) + 1))
+            at += sz
+        return out
+
+    def stats(self) -> dict:
+        """ccsx_gpu_scan_stats: reads scanned, slices launched, sets,
+        candidates, re-runs with the counted capacity, reads scanned on the host."""
+        st = (C.c_uint64 * 6)()
+        if self._L.ccsx_gpu_scan_stats(self._ctx, st, 6) != 0:
+            self._err("ccsx_gpu_scan_stats")
+        return dict(zip(("reads", "slices", "sets", "candidates", "reruns", "host_reads"), (int(x) for x in st)))
 
 
 class Polisher:

@@ -547,6 +547,62 @@ int ccsx_gpu_bc_set(ccsx_bc_ctx *ctx, const char *seqs, const uint32_t *off, con
 int ccsx_gpu_bc_score(ccsx_bc_ctx *ctx, const ccsx_bc_in *z, size_t nz, ccsx_bc_out *out, float *kernel_ms);
 int ccsx_gpu_bc_stats(const ccsx_bc_ctx *ctx, uint64_t *stats, uint32_t n);
 
+/* The adapter scanner (SPEC.md §17 on the device, ccsx_scan.hip): every adapter
+ * of a set, as given and reverse-complemented, is aligned with a free start
+ * along whole CCS reads (+1 / -2 / -2), and every place of a read where an
+ * adapter reaches the threshold comes back as a hit: adapter, orient (1: the
+ * reverse complement), the read's bases [start, end) and the score.  The hits
+ * equal ccsx_scan_host's (include/ccsx_host.h) field for field; ccsx_scan_cut
+ * (there) cuts a read at its hits.
+ *
+ * ccsx_scan_in: one CCS read (ASCII; len may be 0, at most 16,777,215).
+ * ccsx_scan_hit: read = the read's index in the call.
+ *
+ * A scanner context is separate from every other context: its own stream, the
+ * current set's pattern table and its own device arena of at most max_bytes
+ * (0 = 256 MiB), allocated at the first call and grown as slices need.  The
+ * device emits candidates (read, pattern, column, score) into a buffer of the
+ * slice; the host folds the orientations, applies the hit rule, computes the
+ * starts and sorts.  A slice whose candidates outnumber its buffer runs once
+ * more with the counted capacity; if that does not fit the arena the slice is
+ * halved, and a single read that does not fit is scanned by ccsx_scan_host
+ * inside the call.  The calls on one context are serialised.
+ * ccsx_gpu_scan_set: the set for the calls that follow: A sequences (seqs +
+ * off[a], len[a] letters ACGT in either case), 1 <= A <= 64, 1 <= len <= 64,
+ * and the threshold 1 <= T <= 100 (per cent of the adapter's length).  Returns
+ * -1, the earlier set kept, for anything else.
+ * ccsx_gpu_scan: n reads; *hits receives the call's hits sorted by (read, end,
+ * adapter), owned by the context until its next call, *nhits their number,
+ * kernel_ms (may be NULL) the kernels' time by HIP events.  Returns 0, or -1
+ * (also without a set, or for a read longer than 16,777,215).
+ * ccsx_gpu_scan_tracks: the same launch with the bottom rows stored (tests and
+ * tools): track receives, read after read, S_p(j) as int8 at p * (len + 1) + j
+ * for the 2 A patterns, sum over the reads of 2 A (len + 1) bytes in all
+ * (track_bytes must be that).  The reads must fit one slice of the arena.
+ * ccsx_gpu_scan_tile: the columns a lane emits (TC) and its warm-up (WU) for a
+ * set whose longest adapter rounds up to rows (16, 32, 48 or 64); -1 otherwise.
+ * ccsx_gpu_scan_stats: counters so far, the first min(n, 6) of: [0] reads,
+ * [1] slices launched, [2] sets, [3] candidates, [4] re-runs, [5] reads scanned
+ * on the host. */
+typedef struct ccsx_scan_ctx ccsx_scan_ctx;
+typedef struct {
+    const char *ccs;
+    uint32_t len;
+} ccsx_scan_in;
+typedef struct {
+    uint32_t read, adapter, orient, start, end;
+    int32_t score;
+} ccsx_scan_hit;
+int ccsx_gpu_scan_open(int device, uint64_t max_bytes, ccsx_scan_ctx **ctx);
+void ccsx_gpu_scan_close(ccsx_scan_ctx *ctx);
+const char *ccsx_gpu_scan_error(const ccsx_scan_ctx *ctx);
+int ccsx_gpu_scan_set(ccsx_scan_ctx *ctx, const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t A, uint32_t T);
+int ccsx_gpu_scan(ccsx_scan_ctx *ctx, const ccsx_scan_in *reads, size_t n, const ccsx_scan_hit **hits, uint64_t *nhits,
+                  float *kernel_ms);
+int ccsx_gpu_scan_tracks(ccsx_scan_ctx *ctx, const ccsx_scan_in *reads, size_t n, int8_t *track, uint64_t track_bytes);
+int ccsx_gpu_scan_tile(uint32_t rows, uint32_t *TC, uint32_t *WU);
+int ccsx_gpu_scan_stats(const ccsx_scan_ctx *ctx, uint64_t *stats, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

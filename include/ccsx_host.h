@@ -222,6 +222,38 @@ ccsx_barcode_set *ccsx_barcode_read(const char *path);
 uint32_t ccsx_barcode_set_get(const ccsx_barcode_set *s, const char *const **names, const char *const **seqs);
 void ccsx_barcode_set_free(ccsx_barcode_set *s);
 
+/* Adapter scan of whole CCS reads (SPEC.md section 17; the device's
+ * ccsx_gpu_scan gives the same hits).  An adapter file is read with
+ * ccsx_barcode_read.
+ * ccsx_scan_check: 0 for an adapter set (1 <= A <= 64 sequences seqs + off[a]
+ * of 1 <= len[a] <= 64 letters ACGT in either case) and a threshold
+ * 1 <= T <= 100, else -1.
+ * ccsx_scan_host: the definition as a sequential loop over one column per
+ * pattern, for one read ccs / n (ASCII; n may be 0).  Returns the number of
+ * hits and writes the first min(that, cap) of them to hits (may be NULL), by
+ * (end, adapter), read = 0: a first call counts, a second fills.  -1 (nothing
+ * written) for a bad set or T.
+ * ccsx_scan_start: the start of a hit of adapter / L in orientation orient that
+ * ends at column end of ccs / n: end - k*, k* the smallest k in
+ * [0, min(end, 2 L)] that maximises the anchored G(L, k); score (may be NULL)
+ * receives that maximum.  -1 for L outside 1 .. 64 or end > n.
+ * ccsx_scan_cut: the pieces of a read of n bases outside the union of its hits
+ * (nhits of them, as ccsx_scan_host lists them) that have at least Lmin bases,
+ * by b; left / right = the index of the flanking hit, -1 at the read's end.
+ * Returns their number and writes the first min(that, cap) to pieces (may be
+ * NULL).  A read without a hit is the one piece [0, n). */
+typedef struct {
+    uint32_t b, e;
+    int32_t left, right;
+} ccsx_scan_piece;
+int32_t ccsx_scan_check(const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t A, uint32_t T);
+int64_t ccsx_scan_host(const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t A, uint32_t T, const char *ccs,
+                       uint32_t n, ccsx_scan_hit *hits, uint64_t cap);
+int32_t ccsx_scan_start(const char *adapter, uint32_t L, uint32_t orient, const char *ccs, uint32_t n, uint32_t end,
+                        int32_t *score);
+int64_t ccsx_scan_cut(const ccsx_scan_hit *hits, uint64_t nhits, uint32_t n, uint32_t Lmin, ccsx_scan_piece *pieces,
+                      uint64_t cap);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
