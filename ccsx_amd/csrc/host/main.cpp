@@ -206,6 +206,7 @@ int usage()
             "CCSX_TIMING    1: per-chunk / per-batch timing on stderr\n"
             "CCSX_CHUNK     Largest chunk in ZMWs [16384 x contexts; 8192 x contexts with CCSX_ASYNC=0]\n"
             "CCSX_CHUNK0    First chunk in ZMWs [CCSX_CHUNK / 2], growing x4 up to CCSX_CHUNK\n"
+            "CCSX_MIN_BATCH Fewest ZMWs per micro-batch of a chunk [256] (measurement and test override)\n"
             "CCSX_KCFG      Force a kernel configuration (0 latency, 1 occupancy, 2 throughput, 3 solo)\n"
             "CCSX_DEV_SHARE Processes sharing each GPU [1] (each context's memory share shrinks)\n"
             "CCSX_MEM_FRAC  Fraction of each GPU's memory its contexts size their slices from [0.85]\n"
@@ -814,6 +815,11 @@ int main(int argc, char **argv)
     // slowest batch; smaller ones let the contexts end together)
     uint32_t last_batches_per_ctx = 1;
     if (const char *e = getenv("CCSX_LAST_BATCHES")) last_batches_per_ctx = (uint32_t)std::max(1, std::min(64, atoi(e)));
+    // the fewest ZMWs a micro-batch holds (ccsx_partition's floor; CCSX_MIN_BATCH:
+    // a measurement and test override, so that a small input still spreads
+    // over several batches per chunk)
+    uint32_t min_batch = 256;
+    if (const char *e = getenv("CCSX_MIN_BATCH")) min_batch = (uint32_t)std::max(1, atoi(e));
     const bool timing = getenv("CCSX_TIMING") && atoi(getenv("CCSX_TIMING"));
     const bool gpu_strand = getenv("CCSX_GPU_STRAND") && atoi(getenv("CCSX_GPU_STRAND"));
     ccsx_aln_ctx *aln = nullptr;
@@ -1533,7 +1539,7 @@ int main(int argc, char **argv)
             const uint64_t per = slot_bytes / 20 * 19;
             nparts = std::max<uint32_t>(nparts, (uint32_t)((bytes + per - 1) / std::max<uint64_t>(per, 1)));
         }
-        const uint32_t nb = ccsx_partition(cost.data(), n, nparts, 256u, order.data(), bounds.data());
+        const uint32_t nb = ccsx_partition(cost.data(), n, nparts, min_batch, order.data(), bounds.data());
         std::vector<Batch> bs(nb);
         for (uint32_t b = 0; b < nb; ++b) {
             bs[b].chunk = ch;

@@ -12,6 +12,7 @@ import pytest
 import ccsx_amd as cx
 from tests import barcode_cases as bc
 from tests import barcode_ref as R
+from tests import stage_format as F
 from tools.gen_synth import write_subreads
 
 pytestmark = pytest.mark.gpu
@@ -151,21 +152,11 @@ def test_cli_demux(tmp_path, accuracy, fastq):
         assert r.returncode == 0, r.stderr.decode()[-2000:]
     main = open(out_b, "rb").read()
     assert main == open(out_0, "rb").read()
-    # the main output's records: header, bases (and qualities)
-    lines = main.decode().split("\n")[:-1]
-    step = 4 if fastq else 2
-    recs = [(lines[k][1:], lines[k + 1], lines[k + 3] if fastq else None) for k in range(0, len(lines), step)]
+    recs = F.records(main.decode(), fastq)
     assert len(recs) == 13
-    want_d, want_t = "", ["#name\tlen\tbc0\tstrand0\tscore0\tsecond0\tend0\tbc1\tstrand1\tscore1\tsecond1\tend1\tcl\tcr\tcalled0\tcalled1\tassigned\treason"]
+    want_d, want_t, rows = F.demux_files(recs, barcodes, names, fastq, R.score, R.call)
     nassigned = 0
-    for k, (head, seq, qual) in enumerate(recs):
-        r = R.score(barcodes, seq.encode(), 96)
-        cl, cr, called, assigned, reason = R.call(r, [16] * 12, len(seq))
-        row = [head.split()[0], str(len(seq))]
-        for e in r:
-            row += [names[e[0] >> 1], "-" if e[0] & 1 else "+", str(e[1]), str(e[3]), str(e[2])]
-        row += [str(cl), str(cr), str(int(called[0])), str(int(called[1])), str(int(assigned)), cx.BC_REASONS[reason]]
-        want_t.append("\t".join(row))
+    for k, (r, (_, _, _, assigned, _)) in enumerate(rows):
         if k == 6:
             assert not assigned
             continue
@@ -173,12 +164,6 @@ def test_cli_demux(tmp_path, accuracy, fastq):
         nassigned += 1
         i0, i1 = pairs[k - (k > 6)]
         assert {r[0][0] >> 1, r[1][0] >> 1} == {i0, i1}
-        h = f"{head} bc={names[r[0][0] >> 1]}--{names[r[1][0] >> 1]} bs={r[0][1]},{r[1][1]} bx={cl},{cr}"
-        trimmed = seq[cl:len(seq) - cr]
-        if fastq:
-            want_d += f"@{h}\n{trimmed}\n+\n{qual[cl:len(seq) - cr]}\n"
-        else:
-            want_d += f">{h}\n{trimmed}\n"
     assert nassigned == 12
     assert open(dmx).read() == want_d
-    assert open(rep).read() == "\n".join(want_t) + "\n"
+    assert open(rep).read() == want_t

@@ -15,6 +15,7 @@ import ccsx_amd as cx
 from oracle.oracle import batch
 from oracle.oracle import prepare as oracle_prepare
 from oracle.oracle import prepare_segments as oracle_prepare_segments
+from tests.cli_batches import SPREAD, assert_spread
 from tests import basemap_ref as br
 from tests import kinetics_ref as kr
 from tests import pass_ref as pr
@@ -326,15 +327,18 @@ def test_off_means_off(engine):
     assert [g for g, _, _ in ccs_on] == [g for g, _, _ in ccs_off]
 
 
-def _cli_check(tmp_path, src, args, mode, fastq, is_bam=False):
+def _cli_check(tmp_path, src, args, mode, fastq, is_bam=False, env=None, err=None):
     """`args src` with and without -b: the same main output; the -b file
-    rebuilt from the reference on the oracle's preparation and strand flags."""
+    rebuilt from the reference on the oracle's preparation and strand flags.
+    err: a list that receives the stderr of the run with -b."""
     out_b, out_0, strands = str(tmp_path / "out_b"), str(tmp_path / "out_0"), str(tmp_path / "strands")
     # (an eighth of the device per context: the start-up reserves less)
-    env = dict(os.environ, CCSX_DEV_SHARE="8")
+    env = dict(os.environ, **dict(env or {}, CCSX_DEV_SHARE="8"))
     for extra, out in ((["-b", strands], out_b), ([], out_0)):
         r = subprocess.run([BIN] + args + extra + [src, out], capture_output=True, timeout=300, env=env)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
+        if err is not None and extra:
+            err.append(r.stderr)
     assert open(out_b, "rb").read() == open(out_0, "rb").read()
     want, nrec = "", 0
     for movie, hole, subs in cx.read_zmws(src, is_bam):
@@ -360,6 +364,18 @@ def test_cli_by_strand(tmp_path, flags, mode):
     flags = [x for f in flags for x in ([f, str(tmp_path / ("side" + f))] if f in ("-r", "-a", "-s") else [f])]
     nrec, nstrand = _cli_check(tmp_path, fa, ["-A", "-j", "2"] + flags, mode, fastq)
     assert nrec == 12 and nstrand == 24
+
+
+def test_cli_by_strand_async_contexts_order(tmp_path):
+    """Pipelined submit / collect on 2 x 2 contexts, three batches per context
+    and chunk (tests/cli_batches.py's SPREAD, and the run must have spread):
+    the records stay in input order, each ZMW with its own two strands."""
+    fa = str(tmp_path / "in.fa")
+    write(fa, 300, 1000, 6)
+    err = []
+    nrec, nstrand = _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, False, env=SPREAD, err=err)
+    assert nrec == 300 and nstrand == 600
+    assert_spread(err[0])
 
 
 def test_cli_by_strand_bam_input(tmp_path):

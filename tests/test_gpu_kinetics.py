@@ -14,6 +14,7 @@ import ccsx_amd as cx
 from oracle.oracle import batch
 from oracle.oracle import prepare as oracle_prepare
 from oracle.oracle import prepare_segments as oracle_prepare_segments
+from tests.cli_batches import SPREAD, assert_spread
 from tests import basemap_ref as br
 from tests import kinetics_ref as kr
 from tests import pass_ref as pr
@@ -339,9 +340,10 @@ def _tagged_bam(path, nzmw, L, passes, hole0=0, sub=b"C", drop_pw=()):
     write_bam(path, recs)
 
 
-def _cli_check(tmp_path, bam, args, mode, env=None, sub_qual=False):
+def _cli_check(tmp_path, bam, args, mode, env=None, sub_qual=False, stderr=None):
     """`args bam` with and without -k: the same CCS file; the SAM rebuilt from
-    the reference on the oracle's preparation, strand flags and the planes."""
+    the reference on the oracle's preparation, strand flags and the planes.
+    stderr: a list that receives the stderr of the run with -k."""
     out_k, out_0, sam = str(tmp_path / "out_k"), str(tmp_path / "out_0"), str(tmp_path / "kin.sam")
     env = dict(os.environ, **dict(env or {}, CCSX_DEV_SHARE="8"))
     err = b""
@@ -349,6 +351,8 @@ def _cli_check(tmp_path, bam, args, mode, env=None, sub_qual=False):
         r = subprocess.run([BIN] + args + extra + [bam, out], capture_output=True, timeout=300, env=env)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
         err = err or r.stderr
+    if stderr is not None:
+        stderr.append(err)
     assert open(out_k, "rb").read() == open(out_0, "rb").read()
     want, nline, nnone = "@HD\tVN:1.6\tSO:unknown\n", 0, 0
     for movie, hole, subs, ipd, pw in cx.read_zmws(bam, True, kinetics=True):
@@ -380,10 +384,16 @@ def test_cli_kinetics(tmp_path, flags, mode):
 
 def test_cli_kinetics_async_contexts_order(tmp_path):
     """Pipelined submit / collect on two contexts, three batches per context
-    and chunk: the lines stay in input order, each ZMW with its own arrays."""
+    and chunk: the lines stay in input order, each ZMW with its own arrays. The run is
+    tests/cli_batches.py's SPREAD, and must have spread: several chunks, several
+    batches per chunk, several contexts, slots reused.  (Until CCSX_MIN_BATCH
+    existed this test asked for 2 contexts x 3 batches and, 300 ZMWs being
+    fewer than two batches of the 256-ZMW floor, ran one batch on one context.)"""
     bam = str(tmp_path / "in.bam")
     _tagged_bam(bam, 300, 1000, 6)
-    assert _cli_check(tmp_path, bam, ["-j", "4"], 0, env=dict(CCSX_NGPU="2", CCSX_CTX_BATCHES="3")) == (300, 0)
+    err = []
+    assert _cli_check(tmp_path, bam, ["-j", "4"], 0, env=SPREAD, stderr=err) == (300, 0)
+    assert_spread(err[0])
 
 
 def test_cli_frames_and_missing_pw(tmp_path):

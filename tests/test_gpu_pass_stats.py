@@ -13,6 +13,7 @@ import pytest
 import ccsx_amd as cx
 from oracle.oracle import batch
 from oracle.oracle import prepare as oracle_prepare
+from tests.cli_batches import SPREAD, assert_spread
 from tests import pass_ref as pr
 from tests import quality_ref as qr
 from tests.zmw_cases import edge_cases, raw, synth
@@ -254,15 +255,18 @@ def _report(path):
     return rows
 
 
-def _cli_check(tmp_path, src, args, mode, env=None):
+def _cli_check(tmp_path, src, args, mode, env=None, err=None):
     """`args src` with and without -r: the same CCS file; the report's lines
-    from the reference on the oracle's preparation of the same records."""
+    from the reference on the oracle's preparation of the same records.  err: a
+    list that receives the stderr of the run with -r."""
     out_r, out_0, rep = str(tmp_path / "out_r"), str(tmp_path / "out_0"), str(tmp_path / "passes.tsv")
     # (an eighth of the device per context: the start-up reserves less)
     env = dict(os.environ, **dict(env or {}, CCSX_DEV_SHARE="8"))
     for extra, out in ((["-r", rep], out_r), ([], out_0)):
         r = subprocess.run([BIN] + args + extra + [src, out], capture_output=True, timeout=300, env=env)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
+        if err is not None and extra:
+            err.append(r.stderr)
     assert open(out_r, "rb").read() == open(out_0, "rb").read()
     want = []
     nrec = 0
@@ -294,7 +298,13 @@ def test_cli_report(tmp_path, flags, mode):
 
 def test_cli_report_async_contexts_order(tmp_path):
     """Pipelined submit / collect on two contexts, three batches per context
-    and chunk: the report stays in input order, each ZMW with its own records."""
+    and chunk: the report stays in input order, each ZMW with its own records. The run is
+    tests/cli_batches.py's SPREAD, and must have spread: several chunks, several
+    batches per chunk, several contexts, slots reused.  (Until CCSX_MIN_BATCH
+    existed this test asked for 2 contexts x 3 batches and, 300 ZMWs being
+    fewer than two batches of the 256-ZMW floor, ran one batch on one context.)"""
     fa = str(tmp_path / "in.fa")
     write(fa, 300, 1000, 6)
-    assert _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, env=dict(CCSX_NGPU="2", CCSX_CTX_BATCHES="3")) == 300
+    err = []
+    assert _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, env=SPREAD, err=err) == 300
+    assert_spread(err[0])

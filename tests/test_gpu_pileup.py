@@ -14,6 +14,7 @@ import ccsx_amd as cx
 from oracle.oracle import batch
 from oracle.oracle import prepare as oracle_prepare
 from oracle.oracle import prepare_segments as oracle_prepare_segments
+from tests.cli_batches import SPREAD, assert_spread
 from tests import basemap_ref as br
 from tests import pass_ref as pr
 from tests import pileup_ref as pu
@@ -298,15 +299,18 @@ def test_off_means_off(engine):
     assert [g for g, _, _ in ccs_on] == [g for g, _, _ in ccs_off]
 
 
-def _cli_check(tmp_path, src, args, mode, env=None, is_bam=False):
+def _cli_check(tmp_path, src, args, mode, env=None, is_bam=False, err=None):
     """`args src` with and without -s: the same CCS file; the site file rebuilt
-    from the reference on the oracle's preparation and strand flags."""
+    from the reference on the oracle's preparation and strand flags.  err: a
+    list that receives the stderr of the run with -s."""
     out_s, out_0, sites = str(tmp_path / "out_s"), str(tmp_path / "out_0"), str(tmp_path / "sites.tsv")
     # (an eighth of the device per context: the start-up reserves less)
     env = dict(os.environ, **dict(env or {}, CCSX_DEV_SHARE="8"))
     for extra, out in ((["-s", sites], out_s), ([], out_0)):
         r = subprocess.run([BIN] + args + extra + [src, out], capture_output=True, timeout=300, env=env)
         assert r.returncode == 0, r.stderr.decode()[-2000:]
+        if err is not None and extra:
+            err.append(r.stderr)
     assert open(out_s, "rb").read() == open(out_0, "rb").read()
     want, nrec = "", 0
     for movie, hole, subs in cx.read_zmws(src, is_bam):
@@ -335,10 +339,16 @@ def test_cli_sites(tmp_path, flags, mode):
 
 def test_cli_sites_async_contexts_order(tmp_path):
     """Pipelined submit / collect on two contexts, three batches per context
-    and chunk: the sites stay in input order, each ZMW with its own lines."""
+    and chunk: the sites stay in input order, each ZMW with its own lines. The run is
+    tests/cli_batches.py's SPREAD, and must have spread: several chunks, several
+    batches per chunk, several contexts, slots reused.  (Until CCSX_MIN_BATCH
+    existed this test asked for 2 contexts x 3 batches and, 300 ZMWs being
+    fewer than two batches of the 256-ZMW floor, ran one batch on one context.)"""
     fa = str(tmp_path / "in.fa")
     write(fa, 300, 1000, 6)
-    assert _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, env=dict(CCSX_NGPU="2", CCSX_CTX_BATCHES="3"))[0] == 300
+    err = []
+    assert _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, env=SPREAD, err=err)[0] == 300
+    assert_spread(err[0])
 
 
 def test_cli_sites_bam_input(tmp_path):

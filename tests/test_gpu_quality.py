@@ -12,6 +12,7 @@ import pytest
 import ccsx_amd as cx
 from oracle.oracle import batch
 from oracle.oracle import prepare as oracle_prepare
+from tests.cli_batches import SPREAD, assert_spread
 from tests import quality_ref as qr
 from tests.zmw_cases import edge_cases, raw, synth
 from tools.gen_synth import records, write, write_bam
@@ -215,9 +216,10 @@ def _fasta(path):
     return [(lines[i][1:], lines[i + 1]) for i in range(0, len(lines) - 1, 2)]
 
 
-def _cli_check(tmp_path, src, args, mode, env=None, is_bam=False, exclude=()):
+def _cli_check(tmp_path, src, args, mode, env=None, is_bam=False, exclude=(), err=None):
     """`args src` with and without -q: same bases; qualities, np and rq from
-    the reference on the oracle's preparation of the same records."""
+    the reference on the oracle's preparation of the same records.  err: a list
+    that receives the stderr of the run with -q."""
     fq, fa_out = str(tmp_path / "out.fq"), str(tmp_path / "out.fa")
     # (an eighth of the device per context: the start-up reserves less)
     env = dict(env or {}, CCSX_DEV_SHARE="8")
@@ -225,6 +227,8 @@ def _cli_check(tmp_path, src, args, mode, env=None, is_bam=False, exclude=()):
         r = subprocess.run([BIN] + args + extra + [src, out], capture_output=True, timeout=300,
                            env=dict(os.environ, **(env or {})))
         assert r.returncode == 0, r.stderr.decode()[-2000:]
+        if err is not None and extra:
+            err.append(r.stderr)
     got = _fastq(fq)
     assert [(n, s) for n, s, _, _, _ in got] == _fasta(fa_out)
     want = []
@@ -258,10 +262,16 @@ def test_cli_fastq(tmp_path, mode_flag, mode):
 
 def test_cli_fastq_async_contexts_order(tmp_path):
     """Pipelined submit / collect on two contexts, three batches per context
-    and chunk: records stay in input order, each with its own qualities."""
+    and chunk: records stay in input order, each with its own qualities. The run is
+    tests/cli_batches.py's SPREAD, and must have spread: several chunks, several
+    batches per chunk, several contexts, slots reused.  (Until CCSX_MIN_BATCH
+    existed this test asked for 2 contexts x 3 batches and, 300 ZMWs being
+    fewer than two batches of the 256-ZMW floor, ran one batch on one context.)"""
     fa = str(tmp_path / "in.fa")
     write(fa, 300, 1000, 6)
-    assert _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, env=dict(CCSX_NGPU="2", CCSX_CTX_BATCHES="3")) == 300
+    err = []
+    assert _cli_check(tmp_path, fa, ["-A", "-j", "4"], 0, env=SPREAD, err=err) == 300
+    assert_spread(err[0])
 
 
 def test_cli_fastq_bam_input(tmp_path):

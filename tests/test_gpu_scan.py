@@ -16,6 +16,7 @@ import pytest
 import ccsx_amd as cx
 from tests import scan_cases as sc
 from tests import scan_ref as R
+from tests import stage_format as F
 from tools.gen_synth import write_subreads
 
 pytestmark = pytest.mark.gpu
@@ -224,20 +225,9 @@ def test_cli_scan(tmp_path, accuracy, fastq):
         assert r.returncode == 0, r.stderr.decode()[-2000:]
     main = open(out_i, "rb").read()
     assert main == open(out_0, "rb").read()
-    lines = main.decode().split("\n")[:-1]
-    step = 4 if fastq else 2
-    recs = [(lines[k][1:], lines[k + 1], lines[k + 3] if fastq else None) for k in range(0, len(lines), step)]
+    recs = F.records(main.decode(), fastq)
     assert len(recs) == 13
-    want_t, want_p = ["#name\tlen\tadapter\tstrand\tstart\tend\tscore\talen"], ""
-    for k, (head, seq, qual) in enumerate(recs):
-        name = head.split()[0]
-        hits = R.hits(adapters, seq.encode())
-        assert len(hits) == (0 if k == 6 else 2)
-        for a, o, s, e, score in hits:
-            want_t.append("\t".join([name, str(len(seq)), names[a], "-" if o else "+", str(s), str(e), str(score), "25"]))
-        flank = lambda x: "." if x < 0 else names[hits[x][0]] + ("-" if hits[x][1] else "+")  # noqa: E731
-        for b, e, left, right in R.cut(hits, len(seq)):
-            h = f"{name}/{b}_{e} la={flank(left)} ra={flank(right)}"
-            want_p += f"@{h}\n{seq[b:e]}\n+\n{qual[b:e]}\n" if fastq else f">{h}\n{seq[b:e]}\n"
-    assert open(rep).read() == "\n".join(want_t) + "\n"
+    want_t, want_p, found = F.scan_files(recs, adapters, names, fastq, R.hits, R.cut)
+    assert [len(h) for h in found] == [0 if k == 6 else 2 for k in range(13)]
+    assert open(rep).read() == want_t
     assert open(pcs).read() == want_p
