@@ -192,10 +192,11 @@ def build_product(verbose: bool = False) -> str:
     if _stale(diag, host_objs + dobjs):
         _run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", diag] + dobjs + host_objs + ["-lz", "-lpthread"])
     # the C host program
-    main_src = os.path.join(CSRC, "host", "main.cpp")
-    if os.path.exists(main_src) and _stale(BIN, [main_src, LIB] + hdrs):
+    # (records.cpp, the text of its output files, is part of the program only)
+    main_srcs = [os.path.join(CSRC, "host", f) for f in ("main.cpp", "records.cpp")]
+    if os.path.exists(main_srcs[0]) and _stale(BIN, main_srcs + [LIB] + hdrs):
         os.makedirs(os.path.dirname(BIN), exist_ok=True)
-        cmd = [hipcc, "-x", "c++"] + common + ["-D__HIP_PLATFORM_AMD__", "-I" + _rocm_inc(), main_src, "-o", BIN,
+        cmd = [hipcc, "-x", "c++"] + common + ["-D__HIP_PLATFORM_AMD__", "-I" + _rocm_inc()] + main_srcs + ["-o", BIN,
                                                "-L" + HERE, "-lccsx_amd", "-Wl,-rpath,$ORIGIN/..", "-lz", "-lpthread"]
         if verbose:
             print(" ".join(cmd))

@@ -16,6 +16,8 @@
 //     back (main.c:707-717).
 // A ZMW the device cannot finish is reported on stderr and skipped; the other
 // ZMWs of the run are written (the reference has no per-ZMW failure).
+// The side files are one table here (Output); the text of their records and
+// rows is formatted in records.cpp.
 #include <errno.h>
 #include <getopt.h>
 #include <malloc.h>
@@ -40,6 +42,7 @@
 #include "ccsx_gpu.h"
 #include "ccsx_host.h"
 #include "ingest.h"
+#include "records.h"
 
 namespace {
 
@@ -113,6 +116,38 @@ private:
     bool draining_ = false;
 };
 
+// The side files, in the order they are opened.  A further file is a row
+// here, its formatter (records.h), its call in gather_zmw or a stage, and its
+// line in usage()
+enum { kPass, kPaf, kSites, kSam, kStrands, kPolished, kDemux, kDemuxRows, kHits, kPieces, kNumOutputs };
+struct Output {
+    char opt;
+    const char *path;    // null: not asked for
+    FILE *fp;
+    const char *header;  // its first line, or null
+};
+
+struct Options {
+    int verbose = 0, min_subread_len = 5000, max_subread_len = 500000, min_fulllen_count = 3, nthreads = 1;
+    int isbam = 1, split_subread = 1, fastq = 0;
+    Output out[kNumOutputs] = {{'r', nullptr, nullptr, ccsx_rec::kPassHeader}, {'a', nullptr, nullptr, nullptr},
+                               {'s', nullptr, nullptr, nullptr},               {'k', nullptr, nullptr, ccsx_rec::kSamHeader},
+                               {'b', nullptr, nullptr, nullptr},               {'p', nullptr, nullptr, nullptr},
+                               {'d', nullptr, nullptr, nullptr},               {'D', nullptr, nullptr, ccsx_rec::kDemuxHeader},
+                               {'i', nullptr, nullptr, ccsx_rec::kHitHeader},  {'S', nullptr, nullptr, nullptr}};
+    bool has(int k) const { return out[k].path != nullptr; }
+    const char *bc_path = nullptr;  // -B
+    ccsx_rec::SeqSet barcodes;
+    int bc_window = 96, bc_min_pct = 60, bc_min_lead = 3;  // -W -T -L
+    const char *ad_path = nullptr;  // -I
+    ccsx_rec::SeqSet adapters;
+    int ad_min_pct = 75, ad_min_piece = 50;  // -E -e
+    std::unordered_set<std::string> hole_set;  // -X
+    bool have_holes = false;
+    const char *in_path = "-";
+    const char *out_path = nullptr;  // null: stdout
+};
+
 struct Zmw {
     ccsx_ingest::ZmwRef ref;  // the subreads as spans of the input blocks (until assembled)
     std::string movie, hole;
@@ -123,18 +158,10 @@ struct Zmw {
     std::string ccs;
     std::string qual;         // -q: the CCS bases' qualities, Q + 33
     double rq = 0;            // -q: predicted accuracy of the read (ccsx_qual_rq)
-    std::vector<ccsx_pass_stat> pst;  // -r: one record per segment (SPEC.md section 10)
-    std::string paf;          // -a: the PAF lines of its segments (SPEC.md section 11)
-    std::string sites;        // -s: the lines of its discordant sites (SPEC.md section 12)
-    std::string strands;      // -b: the records of its strand consensuses (SPEC.md section 14)
-    std::string polished;     // -p: the record of its polished read (SPEC.md section 15)
-    std::string demux;        // -B -d: the record of its trimmed read, if assigned (SPEC.md section 16)
-    std::string demux_row;    // -B -D: its line of the demultiplexing report
-    std::string scan_rows;    // -I -i: the lines of its adapter hits (SPEC.md section 17)
-    std::string pieces;       // -I -S: the records of its pieces
+    std::string name;         // movie/hole/ccs, once it has a CCS
+    std::string side[kNumOutputs];  // its text in each side file (records.h)
     std::vector<uint8_t> kin;  // -k: the ipd codes of its bases, then the pw codes, parallel to seqs (empty: a subread lacks them)
-    std::string kinline;      // -k: its SAM line (SPEC.md section 13)
-    bool kin_arrays = false;  // -k: ... carries the four arrays
+    bool kin_arrays = false;  // -k: its SAM line carries the four arrays
     int32_t status = 0;
     std::vector<uint32_t> bp;  // -v >= 3: (breakpoint, MSA columns) per shredding round
 };
@@ -537,6 +564,288 @@ std::unordered_set<std::string> exclude_holes(std::string &buf, const char *arg)
     return set;
 }
 
+// The command line into o (main.c:760-826).  Returns 0 to go on, else the
+// exit status, its message printed: the -B and -I sets are read and checked
+// here, before anything is opened
+int parse_options(int argc, char **argv, Options &o)
+{
+    int c;
+    bool ad_opts = false;  // -E or -e given
+    std::string xbuf;      // -X: kputs-appended, ksplit in place (exclude_holes)
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:I:i:S:E:e:")) != -1) {
+        switch (c) {
+        case 'm': o.min_subread_len = atoi(optarg); break;
+        case 'M': o.max_subread_len = atoi(optarg); break;
+        case 'P': o.split_subread = 0; break;
+        case 'A': o.isbam = 0; break;
+        case 'q': o.fastq = 1; break;
+        case 'B': o.bc_path = optarg; break;
+        case 'W': o.bc_window = atoi(optarg); break;
+        case 'T': o.bc_min_pct = atoi(optarg); break;
+        case 'L': o.bc_min_lead = atoi(optarg); break;
+        case 'I': o.ad_path = optarg; break;
+        case 'E': o.ad_min_pct = atoi(optarg), ad_opts = true; break;
+        case 'e': o.ad_min_piece = atoi(optarg), ad_opts = true; break;
+        case 'X':  // main.c:772-782
+            o.have_holes = true;
+            o.hole_set = exclude_holes(xbuf, optarg);
+            break;
+        case 'c':
+            o.min_fulllen_count = atoi(optarg);
+            if (o.min_fulllen_count < 3) {
+                fprintf(stderr, "Error! min fulllen count=[%d] (>=3) !\n", o.min_fulllen_count);
+                return -1;
+            }
+            break;
+        case 'v': o.verbose++; break;
+        case 'j': o.nthreads = atoi(optarg); break;
+        default: {
+            // a side file's path, or -h / an unknown option
+            Output *f = std::find_if(o.out, o.out + kNumOutputs, [c](const Output &x) { return x.opt == c; });
+            if (f == o.out + kNumOutputs) return usage();
+            f->path = optarg;
+        }
+        }
+    }
+    if (o.has(kSam) && !o.isbam) {
+        fprintf(stderr, "Error! -k needs BAM input (the kinetics are the subreads' ip / pw tags): not with -A\n");
+        return 1;
+    }
+    if ((o.has(kDemux) || o.has(kDemuxRows)) && !o.bc_path) {
+        fprintf(stderr, "Error! -d and -D need a barcode file (-B)\n");
+        return 1;
+    }
+    if (o.bc_path) {
+        if (o.bc_window < 1 || o.bc_window > 256) {
+            fprintf(stderr, "Error! -W=[%d] (1..256) !\n", o.bc_window);
+            return 1;
+        }
+        const ccsx_rec::SeqSet &b = o.barcodes;
+        if (!o.barcodes.read(o.bc_path) || ccsx_barcode_check(b.seqs.data(), b.off.data(), b.len.data(), b.size()) != 0) {
+            fprintf(stderr, "Error! %s is not a barcode file: 1..2048 records of 1..64 ACGT letters\n", o.bc_path);
+            return 1;
+        }
+    }
+    if ((o.has(kHits) || o.has(kPieces) || ad_opts) && !o.ad_path) {
+        fprintf(stderr, "Error! -i, -S, -E and -e need an adapter file (-I)\n");
+        return 1;
+    }
+    if (o.ad_path) {
+        if (o.ad_min_pct < 1 || o.ad_min_pct > 100) {
+            fprintf(stderr, "Error! -E=[%d] (1..100) !\n", o.ad_min_pct);
+            return 1;
+        }
+        if (o.ad_min_piece < 0) {
+            fprintf(stderr, "Error! -e=[%d] (>=0) !\n", o.ad_min_piece);
+            return 1;
+        }
+        const ccsx_rec::SeqSet &a = o.adapters;
+        if (!o.adapters.read(o.ad_path) ||
+            ccsx_scan_check(a.seqs.data(), a.off.data(), a.len.data(), a.size(), (uint32_t)o.ad_min_pct) != 0) {
+            fprintf(stderr, "Error! %s is not an adapter file: 1..64 records of 1..64 ACGT letters\n", o.ad_path);
+            return 1;
+        }
+    }
+    // main.c:802-826
+    if (argc - optind > 2) return usage();
+    if (argc - optind >= 1) o.in_path = argv[optind];
+    if (argc - optind == 2 && strcmp(argv[optind + 1], "-") != 0) o.out_path = argv[optind + 1];
+    if (o.nthreads < 1) o.nthreads = 1;
+    return 0;
+}
+
+// a batch in flight on a context: its input arrays live until collected
+struct Flight {
+    Batch b;
+    std::vector<ccsx_zmw_in> in;
+    std::vector<ccsx_zmw_out> out;
+    int slot = -1;
+    double t0 = 0;
+};
+
+// What the results of a batch are turned into text with: the options (the
+// file table, -q, the two sets and their thresholds), the three stage contexts
+// and the locks
+struct Stages {
+    const Options &opt;
+    // -p: the one polisher context, on the first GPU; its results hold until
+    // its next call, so a worker keeps pol_m from its call until it has copied them
+    ccsx_polish_ctx *pol = nullptr;
+    std::mutex pol_m;
+    // -B: the one demultiplexer context, on the first GPU (its calls copy their results out)
+    ccsx_bc_ctx *bc = nullptr;
+    // -I: the one scanner context, on the first GPU; its hits hold until its
+    // next call, so a worker keeps scan_m from its call until it has used them
+    ccsx_scan_ctx *scn = nullptr;
+    std::mutex scan_m;
+    std::mutex err_m;  // stderr
+};
+
+// The engine's results for ZMW i of the batch in f (collected on ctx) into z:
+// its CCS, then one fetch, length check and formatter call per output asked
+// for.  False if the context cannot give one of them (a context error).
+// Qualities first: -k (and later -d and -S) read z.qual and z.rq
+bool gather_zmw(const Options &o, ccsx_ctx *ctx, const Flight &f, size_t i, Zmw &z)
+{
+    using namespace ccsx_rec;
+    const ccsx_zmw_out &r = f.out[i];
+    z.status = r.status;
+    if (r.status) return true;
+    z.ccs.assign(r.ccs, r.len);
+    const std::string zmw = z.movie + "/" + z.hole;
+    z.name = zmw + "/ccs";
+    const size_t nseg = z.seg_len.size();
+    if (o.fastq) {
+        // (f.slot: the collected slot, -1 for a batch ccsx_gpu_run ran)
+        const uint8_t *q = nullptr;
+        uint32_t ql = 0;
+        if (ccsx_gpu_quality(ctx, f.slot, i, &q, &ql) != 0 || ql != r.len) return false;
+        z.rq = ccsx_qual_rq(q, ql);
+        z.qual.resize(ql);
+        for (uint32_t k = 0; k < ql; ++k) z.qual[k] = (char)(q[k] + 33);
+    }
+    if (o.has(kPass)) {
+        const ccsx_pass_stat *st = nullptr;
+        uint32_t ns = 0;
+        if (ccsx_gpu_pass_stats(ctx, f.slot, i, &st, &ns) != 0 || ns != nseg) return false;
+        pass_rows(z.side[kPass], z.name, st, ns, z.seg_off.data(), z.seg_len.data());
+    }
+    if (o.has(kPaf))
+        for (size_t k = 0; k < nseg; ++k) {
+            const uint32_t *mp = nullptr;
+            uint32_t ml = 0;
+            if (ccsx_gpu_base_map(ctx, f.slot, i, (uint32_t)k, &mp, &ml) != 0 || ml != z.seg_len[k]) return false;
+            paf_line(z.side[kPaf], zmw, z.name, k, mp, ml, z.seg_rev[k] != 0, z.seg_off[k], r.len);
+        }
+    if (o.has(kSites)) {
+        const ccsx_pileup *pu = nullptr;
+        uint32_t pl = 0;
+        if (ccsx_gpu_pileup(ctx, f.slot, i, &pu, &pl) != 0 || pl != r.len) return false;
+        site_lines(z.side[kSites], z.name, pu, pl, r.ccs);
+    }
+    const size_t nrev = (size_t)std::count_if(z.seg_rev.begin(), z.seg_rev.end(), [](uint8_t v) { return v != 0; });
+    if (o.has(kSam) && r.len) {
+        const ccsx_kinetics *kr = nullptr;
+        uint32_t kl = 0;
+        if (ccsx_gpu_kinetics(ctx, f.slot, i, &kr, &kl) != 0 || kl != r.len) return false;
+        z.kin_arrays = sam_line(z.side[kSam], z.name, r.ccs, r.len, o.fastq, z.qual, z.rq, nseg, nrev, z.kin.empty() ? nullptr : kr);
+        std::vector<uint8_t>().swap(z.kin);  // (the line is built: the codes go)
+    }
+    if (o.has(kStrands) && r.len)
+        for (int sd = 0; sd < 2; ++sd) {
+            const char *sq = nullptr;
+            const uint8_t *q = nullptr;
+            uint32_t sn = 0;
+            if (ccsx_gpu_by_strand(ctx, f.slot, i, sd, &sq, &q, &sn) != 0) return false;
+            strand_record(z.side[kStrands], o.fastq, z.name, sd, sd ? nrev : nseg - nrev, sq, q, sn);
+        }
+    const uint32_t *lg;
+    uint32_t nr = 0;
+    if (o.verbose > 2 && ccsx_gpu_bp_log(ctx, i, &lg, &nr) == 0) z.bp.assign(lg, lg + 2 * (size_t)nr);
+    return true;
+}
+
+// The batch's ZMWs with a CCS as a stage's input records (In begins with the
+// read and its length); returns their places in the batch
+template <class In>
+std::vector<size_t> reads_with_ccs(const Flight &f, std::vector<In> &in)
+{
+    std::vector<size_t> who;
+    for (size_t i = 0; i < f.b.idx.size(); ++i) {
+        const Zmw &z = f.b.chunk->zs[f.b.idx[i]];
+        if (f.out[i].status || z.ccs.empty()) continue;
+        in.push_back(In{z.ccs.data(), (uint32_t)z.ccs.size()});
+        who.push_back(i);
+    }
+    return who;
+}
+
+// a stage's context failed: its error, once per call
+bool stage_failed(Stages &st, const char *stage, const char *error)
+{
+    std::lock_guard<std::mutex> g(st.err_m);
+    fprintf(stderr, "[ccsx] %s: %s\n", stage, error);
+    return false;
+}
+
+// -p: the batch's ZMWs with a CCS, their drafts and maps as collected on ctx
+bool polish_batch(Stages &st, ccsx_ctx *ctx, const Flight &f)
+{
+    std::vector<Zmw> &zs = f.b.chunk->zs;
+    std::vector<ccsx_polish_in> pin;
+    const std::vector<size_t> who = reads_with_ccs(f, pin);
+    std::vector<std::vector<uint32_t>> maps(pin.size());
+    for (size_t i = 0; i < pin.size(); ++i) {
+        const Zmw &z = zs[f.b.idx[who[i]]];
+        for (size_t k = 0; k < z.seg_len.size(); ++k) {
+            const uint32_t *mp = nullptr;
+            uint32_t ml = 0;
+            if (ccsx_gpu_base_map(ctx, f.slot, who[i], (uint32_t)k, &mp, &ml) != 0 || ml != z.seg_len[k]) return false;
+            maps[i].insert(maps[i].end(), mp, mp + ml);
+        }
+        pin[i].seqs = z.seqs, pin[i].seg_off = z.seg_off.data(), pin[i].seg_len = z.seg_len.data();
+        pin[i].nseg = (uint32_t)z.seg_len.size(), pin[i].map = maps[i].data();
+    }
+    if (pin.empty()) return true;
+    std::vector<ccsx_polish_out> po(pin.size());
+    std::lock_guard<std::mutex> g(st.pol_m);
+    if (ccsx_gpu_polish(st.pol, pin.data(), pin.size(), po.data(), nullptr) != 0)
+        return stage_failed(st, "polisher", ccsx_gpu_polish_error(st.pol));
+    for (size_t i = 0; i < pin.size(); ++i) {
+        Zmw &z = zs[f.b.idx[who[i]]];
+        if (po[i].status || !po[i].len) continue;  // (a collected map is never a bad one)
+        ccsx_rec::polished_record(z.side[kPolished], st.opt.fastq, z.name, po[i].seq, po[i].qual, po[i].len);
+    }
+    return true;
+}
+
+// -B: the batch's CCS reads are scored here; then the call, the trimmed record and the report line
+bool demux_batch(Stages &st, const Flight &f)
+{
+    const Options &o = st.opt;
+    std::vector<ccsx_bc_in> bin;
+    const std::vector<size_t> who = reads_with_ccs(f, bin);
+    std::vector<ccsx_bc_out> bo(bin.size());
+    if (!bin.empty() && ccsx_gpu_bc_score(st.bc, bin.data(), bin.size(), bo.data(), nullptr) != 0)
+        return stage_failed(st, "demultiplexer", ccsx_gpu_bc_error(st.bc));
+    for (size_t i = 0; i < bin.size(); ++i) {
+        Zmw &z = f.b.chunk->zs[f.b.idx[who[i]]];
+        const uint32_t n = (uint32_t)z.ccs.size();
+        ccsx_bc_call call;
+        ccsx_barcode_call(&bo[i], o.barcodes.len.data(), o.barcodes.size(), n, o.bc_min_pct, o.bc_min_lead, &call);
+        if (o.has(kDemuxRows)) ccsx_rec::demux_row(z.side[kDemuxRows], z.name, n, bo[i], call, o.barcodes.names);
+        if (o.has(kDemux))
+            ccsx_rec::demux_record(z.side[kDemux], o.fastq, ccsx_rec::read_header(z.name, o.fastq, z.seg_len.size(), z.rq), z.ccs,
+                                   z.qual, bo[i], call, o.barcodes.names);
+    }
+    return true;
+}
+
+// -I: the batch's CCS reads are scanned here; then the report lines and the pieces
+bool scan_batch(Stages &st, const Flight &f)
+{
+    const Options &o = st.opt;
+    std::vector<ccsx_scan_in> sin;
+    const std::vector<size_t> who = reads_with_ccs(f, sin);
+    std::lock_guard<std::mutex> gs(st.scan_m);
+    const ccsx_scan_hit *hits = nullptr;
+    uint64_t nhits = 0;
+    if (!sin.empty() && ccsx_gpu_scan(st.scn, sin.data(), sin.size(), &hits, &nhits, nullptr) != 0)
+        return stage_failed(st, "scanner", ccsx_gpu_scan_error(st.scn));
+    uint64_t h0 = 0;
+    for (size_t i = 0; i < sin.size(); ++i) {
+        Zmw &z = f.b.chunk->zs[f.b.idx[who[i]]];
+        uint64_t h1 = h0;
+        while (h1 < nhits && hits[h1].read == i) ++h1;
+        if (o.has(kHits)) ccsx_rec::hit_rows(z.side[kHits], z.name, (uint32_t)z.ccs.size(), hits + h0, h1 - h0, o.adapters);
+        if (o.has(kPieces))
+            ccsx_rec::piece_records(z.side[kPieces], o.fastq, z.name, z.ccs, z.qual, hits + h0, h1 - h0, o.adapters,
+                                    (uint32_t)o.ad_min_piece);
+        h0 = h1;
+    }
+    return true;
+}
+
 }  // namespace
 
 // CCSX_CHUNK / CCSX_CHUNK0 (measurement overrides) over the default last
@@ -570,148 +879,14 @@ int main(int argc, char **argv)
         mallopt(M_MMAP_THRESHOLD, 32 << 20);
         mallopt(M_TRIM_THRESHOLD, 1 << 30);
     }
-    int c, verbose = 0, min_subread_len = 5000, max_subread_len = 500000, min_fulllen_count = 3, nthreads = 1;
-    int isbam = 1, split_subread = 1, fastq = 0;
-    const char *report_path = nullptr;  // -r
-    const char *paf_path = nullptr;     // -a
-    const char *site_path = nullptr;    // -s
-    const char *kin_path = nullptr;     // -k
-    const char *strand_path = nullptr;  // -b
-    const char *polish_path = nullptr;  // -p
-    const char *bc_path = nullptr;      // -B
-    const char *demux_path = nullptr;   // -d
-    const char *bcrep_path = nullptr;   // -D
-    int bc_window = 96, bc_min_pct = 60, bc_min_lead = 3;  // -W -T -L
-    const char *ad_path = nullptr;      // -I
-    const char *hit_path = nullptr;     // -i
-    const char *piece_path = nullptr;   // -S
-    int ad_min_pct = 75, ad_min_piece = 50;  // -E -e
-    bool ad_opts = false;               // -E or -e given
-    std::unordered_set<std::string> hole_set;
-    std::string xbuf;  // -X: kputs-appended, ksplit in place (exclude_holes)
-    bool have_holes = false;
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:I:i:S:E:e:")) != -1) {
-        switch (c) {
-        case 'm': min_subread_len = atoi(optarg); break;
-        case 'M': max_subread_len = atoi(optarg); break;
-        case 'P': split_subread = 0; break;
-        case 'A': isbam = 0; break;
-        case 'q': fastq = 1; break;
-        case 'r': report_path = optarg; break;
-        case 'a': paf_path = optarg; break;
-        case 's': site_path = optarg; break;
-        case 'k': kin_path = optarg; break;
-        case 'b': strand_path = optarg; break;
-        case 'p': polish_path = optarg; break;
-        case 'B': bc_path = optarg; break;
-        case 'd': demux_path = optarg; break;
-        case 'D': bcrep_path = optarg; break;
-        case 'W': bc_window = atoi(optarg); break;
-        case 'T': bc_min_pct = atoi(optarg); break;
-        case 'L': bc_min_lead = atoi(optarg); break;
-        case 'I': ad_path = optarg; break;
-        case 'i': hit_path = optarg; break;
-        case 'S': piece_path = optarg; break;
-        case 'E': ad_min_pct = atoi(optarg), ad_opts = true; break;
-        case 'e': ad_min_piece = atoi(optarg), ad_opts = true; break;
-        case 'X':  // main.c:772-782
-            have_holes = true;
-            hole_set = exclude_holes(xbuf, optarg);
-            break;
-        case 'c':
-            min_fulllen_count = atoi(optarg);
-            if (min_fulllen_count < 3) {
-                fprintf(stderr, "Error! min fulllen count=[%d] (>=3) !\n", min_fulllen_count);
-                return -1;
-            }
-            break;
-        case 'v': verbose++; break;
-        case 'j': nthreads = atoi(optarg); break;
-        default: return usage();
-        }
-    }
-    if (kin_path && !isbam) {
-        fprintf(stderr, "Error! -k needs BAM input (the kinetics are the subreads' ip / pw tags): not with -A\n");
-        return 1;
-    }
-    // -B: the barcode set, read and checked before anything else is opened
-    std::vector<std::string> bc_names;
-    std::string bc_seqs;
-    std::vector<uint32_t> bc_off, bc_len;
-    if ((demux_path || bcrep_path) && !bc_path) {
-        fprintf(stderr, "Error! -d and -D need a barcode file (-B)\n");
-        return 1;
-    }
-    if (bc_path) {
-        if (bc_window < 1 || bc_window > 256) {
-            fprintf(stderr, "Error! -W=[%d] (1..256) !\n", bc_window);
-            return 1;
-        }
-        ccsx_barcode_set *bs = ccsx_barcode_read(bc_path);
-        const char *const *nm = nullptr, *const *sq = nullptr;
-        const uint32_t nb = ccsx_barcode_set_get(bs, &nm, &sq);
-        for (uint32_t b = 0; b < nb; ++b) {
-            bc_names.push_back(nm[b]);
-            bc_off.push_back((uint32_t)bc_seqs.size());
-            bc_len.push_back((uint32_t)strlen(sq[b]));
-            bc_seqs += sq[b];
-        }
-        ccsx_barcode_set_free(bs);
-        if (!nb || ccsx_barcode_check(bc_seqs.data(), bc_off.data(), bc_len.data(), nb) != 0) {
-            fprintf(stderr, "Error! %s is not a barcode file: 1..2048 records of 1..64 ACGT letters\n", bc_path);
-            return 1;
-        }
-    }
-    // -I: the adapter set, read and checked before anything else is opened
-    std::vector<std::string> ad_names;
-    std::string ad_seqs;
-    std::vector<uint32_t> ad_off, ad_len;
-    if ((hit_path || piece_path || ad_opts) && !ad_path) {
-        fprintf(stderr, "Error! -i, -S, -E and -e need an adapter file (-I)\n");
-        return 1;
-    }
-    if (ad_path) {
-        if (ad_min_pct < 1 || ad_min_pct > 100) {
-            fprintf(stderr, "Error! -E=[%d] (1..100) !\n", ad_min_pct);
-            return 1;
-        }
-        if (ad_min_piece < 0) {
-            fprintf(stderr, "Error! -e=[%d] (>=0) !\n", ad_min_piece);
-            return 1;
-        }
-        ccsx_barcode_set *as = ccsx_barcode_read(ad_path);
-        const char *const *nm = nullptr, *const *sq = nullptr;
-        const uint32_t na = ccsx_barcode_set_get(as, &nm, &sq);
-        for (uint32_t a = 0; a < na; ++a) {
-            ad_names.push_back(nm[a]);
-            ad_off.push_back((uint32_t)ad_seqs.size());
-            ad_len.push_back((uint32_t)strlen(sq[a]));
-            ad_seqs += sq[a];
-        }
-        ccsx_barcode_set_free(as);
-        if (!na || ccsx_scan_check(ad_seqs.data(), ad_off.data(), ad_len.data(), na, (uint32_t)ad_min_pct) != 0) {
-            fprintf(stderr, "Error! %s is not an adapter file: 1..64 records of 1..64 ACGT letters\n", ad_path);
-            return 1;
-        }
-    }
-    // main.c:802-826
-    const char *in_path = "-";
-    FILE *fp_out = nullptr;
-    if (argc - optind == 0) {
-        fp_out = stdout;
-    } else if (argc - optind == 1) {
-        in_path = argv[optind];
-        fp_out = stdout;
-    } else if (argc - optind == 2) {
-        in_path = argv[optind];
-        fp_out = strcmp(argv[optind + 1], "-") == 0 ? stdout : fopen(argv[optind + 1], "w+");
-    } else {
-        return usage();
-    }
-    if (nthreads < 1) nthreads = 1;
+    Options opt;
+    if (const int status = parse_options(argc, argv, opt)) return status;
+    const int verbose = opt.verbose, split_subread = opt.split_subread, fastq = opt.fastq, nthreads = opt.nthreads;
+    Output *const outs = opt.out;
+    FILE *fp_out = opt.out_path ? fopen(opt.out_path, "w+") : stdout;
     // step 0's input: blocks decompressed ahead on a producer thread (BGZF
     // members inflated on the -j threads), records parsed as spans
-    auto rd = ccsx_ingest::ZmwSource::open(in_path, isbam != 0, nthreads);
+    auto rd = ccsx_ingest::ZmwSource::open(opt.in_path, opt.isbam != 0, nthreads);
     if (!rd) {
         fprintf(stderr, "Error: Failed to open infile!\n");
         return 1;
@@ -720,53 +895,13 @@ int main(int argc, char **argv)
         fprintf(stderr, "Cannot open file for write!\n");
         return 1;
     }
-    FILE *fp_rep = report_path ? fopen(report_path, "w") : nullptr;
-    if (report_path && !fp_rep) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_paf = paf_path ? fopen(paf_path, "w") : nullptr;
-    if (paf_path && !fp_paf) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_site = site_path ? fopen(site_path, "w") : nullptr;
-    if (site_path && !fp_site) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_kin = kin_path ? fopen(kin_path, "w") : nullptr;
-    if (kin_path && !fp_kin) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_str = strand_path ? fopen(strand_path, "w") : nullptr;
-    if (strand_path && !fp_str) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_pol = polish_path ? fopen(polish_path, "w") : nullptr;
-    if (polish_path && !fp_pol) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_dmx = demux_path ? fopen(demux_path, "w") : nullptr;
-    FILE *fp_bcr = bcrep_path ? fopen(bcrep_path, "w") : nullptr;
-    if ((demux_path && !fp_dmx) || (bcrep_path && !fp_bcr)) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    FILE *fp_hit = hit_path ? fopen(hit_path, "w") : nullptr;
-    FILE *fp_pcs = piece_path ? fopen(piece_path, "w") : nullptr;
-    if ((hit_path && !fp_hit) || (piece_path && !fp_pcs)) {
-        fprintf(stderr, "Cannot open file for write!\n");
-        return 1;
-    }
-    if (fp_hit) fprintf(fp_hit, "#name\tlen\tadapter\tstrand\tstart\tend\tscore\talen\n");
-    if (fp_bcr)
-        fprintf(fp_bcr, "#name\tlen\tbc0\tstrand0\tscore0\tsecond0\tend0\tbc1\tstrand1\tscore1\tsecond1\tend1\tcl\tcr\tcalled0\tcalled1\tassigned\treason\n");
-    if (fp_kin) fprintf(fp_kin, "@HD\tVN:1.6\tSO:unknown\n");
-    if (fp_rep) fprintf(fp_rep, "#name\tpass\tsbeg\tslen\tmatch\tmismatch\tins\tdel\tcbeg\tcend\tidentity\n");
+    for (Output *f = outs; f < outs + kNumOutputs; ++f)
+        if (f->path && !(f->fp = fopen(f->path, "w"))) {
+            fprintf(stderr, "Cannot open file for write!\n");
+            return 1;
+        }
+    for (Output *f = outs; f < outs + kNumOutputs; ++f)
+        if (f->fp && f->header) fputs(f->header, f->fp);
     // step 1 pipelined per context (ccsx_gpu_submit / ccsx_gpu_collect: the
     // next batch is launched before the previous one is collected);
     // CCSX_ASYNC=0: one ccsx_gpu_run per batch (also for the -v >= 3
@@ -823,16 +958,7 @@ int main(int argc, char **argv)
     const bool timing = getenv("CCSX_TIMING") && atoi(getenv("CCSX_TIMING"));
     const bool gpu_strand = getenv("CCSX_GPU_STRAND") && atoi(getenv("CCSX_GPU_STRAND"));
     ccsx_aln_ctx *aln = nullptr;
-    // -p: the one polisher context, on the first GPU; its results hold until
-    // its next call, so a worker keeps pol_m from its call until it has copied them
-    ccsx_polish_ctx *pol = nullptr;
-    std::mutex pol_m;
-    // -B: the one demultiplexer context, on the first GPU (its calls copy their results out)
-    ccsx_bc_ctx *bc = nullptr;
-    // -I: the one scanner context, on the first GPU; its hits hold until its
-    // next call, so a worker keeps scan_m from its call until it has used them
-    ccsx_scan_ctx *scn = nullptr;
-    std::mutex scan_m;
+    Stages st{opt};  // the stage contexts open with the devices (below)
     bool aln_tried = false;
     const auto tstart = std::chrono::steady_clock::now();
     auto now_ms = [tstart]() {
@@ -851,7 +977,6 @@ int main(int argc, char **argv)
     std::atomic<bool> fatal(false);
     std::atomic<uint64_t> cells_total(0);  // DP cells the devices computed (CCSX_TIMING report)
     std::atomic<int> workers_busy(0);      // pipelined workers still running
-    std::mutex err_m;
 
     // test hook: the device reports this hole as failed (tests/test_gpu_cli.py)
     const std::string fault_hole = getenv("CCSX_FAULT_HOLE") ? getenv("CCSX_FAULT_HOLE") : "";
@@ -861,14 +986,6 @@ int main(int argc, char **argv)
     std::atomic<long> batches_seen(0);
 
     // step 1, device side: one worker per context
-    // a batch in flight on a context: its input arrays live until collected
-    struct Flight {
-        Batch b;
-        std::vector<ccsx_zmw_in> in;
-        std::vector<ccsx_zmw_out> out;
-        int slot = -1;
-        double t0 = 0;
-    };
     auto prepare_in = [&](int w, Flight &f) {
         Chunk &ch = *f.b.chunk;
         f.in.resize(f.b.idx.size());
@@ -885,331 +1002,19 @@ int main(int argc, char **argv)
     auto finish = [&](int w, Flight &f, int r) {
         Chunk &ch = *f.b.chunk;
         if (fatal_after >= 0 && batches_seen.fetch_add(1) >= fatal_after) r = -9;
-        bool qfail = false;  // -q / -r / -a / -s / -k / -b: the batch's qualities, pass records, maps, pileups, kinetics or strand consensuses are missing (a context error)
-        if (r == 0 || r == -2) {
-            // -2: some ZMWs failed on the device, the rest are valid
+        bool ok = r == 0 || r == -2;  // -2: some ZMWs failed on the device, the rest are valid
+        if (ok) {
             uint64_t cells = 0;
             for (size_t i = 0; i < f.b.idx.size(); ++i) cells += f.out[i].cells;
             cells_total += cells;
-            for (size_t i = 0; i < f.b.idx.size(); ++i) {
-                Zmw &z = ch.zs[f.b.idx[i]];
-                z.status = f.out[i].status;
-                if (!f.out[i].status) z.ccs.assign(f.out[i].ccs, f.out[i].len);
-                if (fastq && !f.out[i].status) {
-                    // (f.slot: the collected slot, -1 for a batch ccsx_gpu_run ran)
-                    const uint8_t *q = nullptr;
-                    uint32_t ql = 0;
-                    if (ccsx_gpu_quality(ctx[w], f.slot, i, &q, &ql) != 0 || ql != f.out[i].len) {
-                        qfail = true;
-                        break;
-                    }
-                    z.rq = ccsx_qual_rq(q, ql);
-                    z.qual.resize(ql);
-                    for (uint32_t k = 0; k < ql; ++k) z.qual[k] = (char)(q[k] + 33);
-                }
-                if (fp_rep && !f.out[i].status) {
-                    const ccsx_pass_stat *st = nullptr;
-                    uint32_t ns = 0;
-                    if (ccsx_gpu_pass_stats(ctx[w], f.slot, i, &st, &ns) != 0 || ns != z.seg_len.size()) {
-                        qfail = true;
-                        break;
-                    }
-                    z.pst.assign(st, st + ns);
-                }
-                if (fp_paf && !f.out[i].status) {
-                    // one PAF line per segment with an aligned base; query
-                    // coordinates on the subread's own strand, CIGAR in CCS order
-                    std::string cg;
-                    char head[160];
-                    for (size_t k = 0; k < z.seg_len.size() && !qfail; ++k) {
-                        const uint32_t *mp = nullptr;
-                        uint32_t ml = 0;
-                        if (ccsx_gpu_base_map(ctx[w], f.slot, i, (uint32_t)k, &mp, &ml) != 0 || ml != z.seg_len[k]) {
-                            qfail = true;
-                            break;
-                        }
-                        ccsx_map_aln a;
-                        const long n = ccsx_map_cigar(mp, ml, &a, nullptr, 0);
-                        if (n < 0) continue;
-                        cg.resize((size_t)n + 1);
-                        (void)ccsx_map_cigar(mp, ml, &a, &cg[0], cg.size());
-                        cg.resize((size_t)n);
-                        const bool rev = z.seg_rev[k] != 0;
-                        snprintf(head, sizeof head, "/%zu\t%u\t%u\t%u\t%c\t", k, ml, rev ? ml - a.qe : a.qs, rev ? ml - a.qs : a.qe,
-                                 rev ? '-' : '+');
-                        z.paf += z.movie + "/" + z.hole + head + z.movie + "/" + z.hole + "/ccs";
-                        snprintf(head, sizeof head, "\t%u\t%u\t%u\t%u\t%u\t255\tsb:i:%u\tcg:Z:", f.out[i].len, a.ts, a.te, a.n_eq,
-                                 a.n_eq + a.n_x + a.n_ins + a.n_del, z.seg_off[k]);
-                        z.paf += head;
-                        z.paf += cg;
-                        z.paf += '\n';
-                    }
-                    if (qfail) break;
-                }
-                if (fp_site && !f.out[i].status) {
-                    // one line per position whose two strands call differently
-                    const ccsx_pileup *pu = nullptr;
-                    uint32_t pl = 0;
-                    if (ccsx_gpu_pileup(ctx[w], f.slot, i, &pu, &pl) != 0 || pl != f.out[i].len) {
-                        qfail = true;
-                        break;
-                    }
-                    char line[160];
-                    for (uint32_t p = 0; p < pl; ++p) {
-                        const int cf = ccsx_pileup_call(&pu[p], 0), cr = ccsx_pileup_call(&pu[p], 1);
-                        if (cf < 0 || cr < 0 || cf == cr) continue;
-                        const uint8_t *a = pu[p].fwd, *b = pu[p].rev;
-                        snprintf(line, sizeof line, "/ccs\t%u\t%c\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", p,
-                                 f.out[i].ccs[p], "ACGT-"[cf], "ACGT-"[cr], a[0], a[1], a[2], a[3], a[4], a[5], b[0], b[1], b[2],
-                                 b[3], b[4], b[5]);
-                        z.sites += z.movie + "/" + z.hole + line;
-                    }
-                }
-                if (fp_kin && !f.out[i].status && f.out[i].len) {
-                    // the ZMW's SAM line; the four arrays only where it came with kinetics
-                    const ccsx_kinetics *kr = nullptr;
-                    uint32_t kl = 0;
-                    if (ccsx_gpu_kinetics(ctx[w], f.slot, i, &kr, &kl) != 0 || kl != f.out[i].len) {
-                        qfail = true;
-                        break;
-                    }
-                    size_t nrev = 0;
-                    for (uint8_t v : z.seg_rev) nrev += v != 0;
-                    char num[96];
-                    std::string &s = z.kinline;
-                    s = z.movie + "/" + z.hole + "/ccs\t4\t*\t0\t255\t*\t*\t0\t0\t";
-                    s.append(f.out[i].ccs, f.out[i].len);
-                    s += '\t';
-                    if (fastq) s += z.qual;
-                    else s += '*';
-                    snprintf(num, sizeof num, "\tnp:i:%zu", z.seg_len.size());
-                    s += num;
-                    if (fastq) {
-                        snprintf(num, sizeof num, "\trq:f:%.6f", z.rq);
-                        s += num;
-                    }
-                    snprintf(num, sizeof num, "\tfn:i:%zu\trn:i:%zu", z.seg_rev.size() - nrev, nrev);
-                    s += num;
-                    z.kin_arrays = !z.kin.empty();
-                    if (z.kin_arrays) {
-                        const long n = ccsx_kinetics_tags(kr, kl, nullptr, 0);
-                        const size_t at = s.size() + 1;
-                        s += '\t';
-                        s.resize(at + (size_t)n + 1);
-                        (void)ccsx_kinetics_tags(kr, kl, &s[at], (size_t)n + 1);
-                        s.resize(at + (size_t)n);
-                    }
-                    s += '\n';
-                    std::vector<uint8_t>().swap(z.kin);
-                }
-                if (fp_str && !f.out[i].status && f.out[i].len) {
-                    // the forward, then the reverse strand's record, laid out as the main output's
-                    char head[96];
-                    for (int sd = 0; sd < 2 && !qfail; ++sd) {
-                        const char *sq = nullptr;
-                        const uint8_t *q = nullptr;
-                        uint32_t sn = 0;
-                        if (ccsx_gpu_by_strand(ctx[w], f.slot, i, sd, &sq, &q, &sn) != 0) {
-                            qfail = true;
-                            break;
-                        }
-                        if (!sn) continue;
-                        size_t np = 0;
-                        for (uint8_t v : z.seg_rev) np += (v != 0) == (sd != 0);
-                        std::string &s = z.strands;
-                        s += fastq ? '@' : '>';
-                        s += z.movie + "/" + z.hole + (sd ? "/ccs/rev" : "/ccs/fwd");
-                        if (fastq) {
-                            snprintf(head, sizeof head, " np=%zu rq=%.6f", np, ccsx_qual_rq(q, sn));
-                            s += head;
-                        }
-                        s += '\n';
-                        s.append(sq, sn);
-                        s += '\n';
-                        if (fastq) {
-                            s += "+\n";
-                            for (uint32_t k = 0; k < sn; ++k) s += (char)(q[k] + 33);
-                            s += '\n';
-                        }
-                    }
-                    if (qfail) break;
-                }
-                const uint32_t *lg;
-                uint32_t nr = 0;
-                if (verbose > 2 && !f.out[i].status && ccsx_gpu_bp_log(ctx[w], i, &lg, &nr) == 0)
-                    z.bp.assign(lg, lg + 2 * (size_t)nr);
-            }
-            if (pol && !qfail) {
-                // -p: the batch's ZMWs with a CCS, their drafts and maps as collected
-                std::vector<ccsx_polish_in> pin;
-                std::vector<size_t> who;
-                std::vector<std::vector<uint32_t>> maps;
-                for (size_t i = 0; i < f.b.idx.size() && !qfail; ++i) {
-                    Zmw &z = ch.zs[f.b.idx[i]];
-                    if (f.out[i].status || z.ccs.empty()) continue;
-                    std::vector<uint32_t> m;
-                    for (size_t k = 0; k < z.seg_len.size(); ++k) {
-                        const uint32_t *mp = nullptr;
-                        uint32_t ml = 0;
-                        if (ccsx_gpu_base_map(ctx[w], f.slot, i, (uint32_t)k, &mp, &ml) != 0 || ml != z.seg_len[k]) {
-                            qfail = true;
-                            break;
-                        }
-                        m.insert(m.end(), mp, mp + ml);
-                    }
-                    pin.push_back(ccsx_polish_in{z.ccs.data(), (uint32_t)z.ccs.size(), z.seqs, z.seg_off.data(), z.seg_len.data(),
-                                                 (uint32_t)z.seg_len.size(), nullptr});
-                    who.push_back(f.b.idx[i]);
-                    maps.push_back(std::move(m));
-                }
-                for (size_t i = 0; i < pin.size(); ++i) pin[i].map = maps[i].data();
-                if (!qfail && !pin.empty()) {
-                    std::vector<ccsx_polish_out> po(pin.size());
-                    std::lock_guard<std::mutex> g(pol_m);
-                    if (ccsx_gpu_polish(pol, pin.data(), pin.size(), po.data(), nullptr) != 0) {
-                        std::lock_guard<std::mutex> g2(err_m);
-                        fprintf(stderr, "[ccsx] polisher: %s\n", ccsx_gpu_polish_error(pol));
-                        qfail = true;
-                    }
-                    for (size_t i = 0; i < pin.size() && !qfail; ++i) {
-                        Zmw &z = ch.zs[who[i]];
-                        if (po[i].status || !po[i].len) continue;  // (a collected map is never a bad one)
-                        std::string &s = z.polished;
-                        s += fastq ? '@' : '>';
-                        s += z.movie + "/" + z.hole + "/ccs/polished\n";
-                        s.append(po[i].seq, po[i].len);
-                        s += '\n';
-                        if (fastq) {
-                            s += "+\n";
-                            for (uint32_t k = 0; k < po[i].len; ++k) s += (char)(po[i].qual[k] + 33);
-                            s += '\n';
-                        }
-                    }
-                }
-            }
-            if (bc && !qfail) {
-                // -B: the batch's CCS reads are scored here; then the call, the trimmed record and the report line
-                std::vector<ccsx_bc_in> bin;
-                std::vector<size_t> who;
-                for (size_t i = 0; i < f.b.idx.size(); ++i) {
-                    const Zmw &z = ch.zs[f.b.idx[i]];
-                    if (f.out[i].status || z.ccs.empty()) continue;
-                    bin.push_back(ccsx_bc_in{z.ccs.data(), (uint32_t)z.ccs.size()});
-                    who.push_back(f.b.idx[i]);
-                }
-                std::vector<ccsx_bc_out> bo(bin.size());
-                if (!bin.empty() && ccsx_gpu_bc_score(bc, bin.data(), bin.size(), bo.data(), nullptr) != 0) {
-                    std::lock_guard<std::mutex> g2(err_m);
-                    fprintf(stderr, "[ccsx] demultiplexer: %s\n", ccsx_gpu_bc_error(bc));
-                    qfail = true;
-                }
-                static const char *const why[] = {"ok", "end0", "end1", "ends", "insert"};
-                for (size_t i = 0; i < bin.size() && !qfail; ++i) {
-                    Zmw &z = ch.zs[who[i]];
-                    const uint32_t n = (uint32_t)z.ccs.size();
-                    ccsx_bc_call call;
-                    ccsx_barcode_call(&bo[i], bc_len.data(), (uint32_t)bc_len.size(), n, bc_min_pct, bc_min_lead, &call);
-                    const ccsx_bc_end *e = bo[i].e;
-                    char num[160];
-                    if (fp_bcr) {
-                        std::string &s = z.demux_row;
-                        snprintf(num, sizeof num, "/ccs\t%u", n);
-                        s = z.movie + "/" + z.hole + num;
-                        for (int k = 0; k < 2; ++k) {
-                            s += '\t' + bc_names[(size_t)e[k].pattern >> 1];
-                            const char o = (e[k].pattern & 1) ? '-' : '+';
-                            if (e[k].second_pattern < 0) snprintf(num, sizeof num, "\t%c\t%d\t.\t%d", o, e[k].score, e[k].end);
-                            else snprintf(num, sizeof num, "\t%c\t%d\t%d\t%d", o, e[k].score, e[k].second, e[k].end);
-                            s += num;
-                        }
-                        snprintf(num, sizeof num, "\t%u\t%u\t%d\t%d\t%d\t%s\n", call.cl, call.cr, call.called[0], call.called[1],
-                                 call.assigned, why[call.reason]);
-                        s += num;
-                    }
-                    if (fp_dmx && call.assigned) {
-                        // the read's own header, then the pair, the two scores and the two clips
-                        std::string &s = z.demux;
-                        s += fastq ? '@' : '>';
-                        s += z.movie + "/" + z.hole + "/ccs";
-                        if (fastq) {
-                            snprintf(num, sizeof num, " np=%zu rq=%.6f", z.seg_len.size(), z.rq);
-                            s += num;
-                        }
-                        s += " bc=" + bc_names[(size_t)e[0].pattern >> 1] + "--" + bc_names[(size_t)e[1].pattern >> 1];
-                        snprintf(num, sizeof num, " bs=%d,%d bx=%u,%u\n", e[0].score, e[1].score, call.cl, call.cr);
-                        s += num;
-                        s.append(z.ccs, call.cl, n - call.cl - call.cr);
-                        s += '\n';
-                        if (fastq) {
-                            s += "+\n";
-                            s.append(z.qual, call.cl, n - call.cl - call.cr);
-                            s += '\n';
-                        }
-                    }
-                }
-            }
-            if (scn && !qfail) {
-                // -I: the batch's CCS reads are scanned here; then the report lines and the pieces
-                std::vector<ccsx_scan_in> sin;
-                std::vector<size_t> who;
-                for (size_t i = 0; i < f.b.idx.size(); ++i) {
-                    const Zmw &z = ch.zs[f.b.idx[i]];
-                    if (f.out[i].status || z.ccs.empty()) continue;
-                    sin.push_back(ccsx_scan_in{z.ccs.data(), (uint32_t)z.ccs.size()});
-                    who.push_back(f.b.idx[i]);
-                }
-                std::lock_guard<std::mutex> gs(scan_m);
-                const ccsx_scan_hit *hits = nullptr;
-                uint64_t nhits = 0;
-                if (!sin.empty() && ccsx_gpu_scan(scn, sin.data(), sin.size(), &hits, &nhits, nullptr) != 0) {
-                    std::lock_guard<std::mutex> g2(err_m);
-                    fprintf(stderr, "[ccsx] scanner: %s\n", ccsx_gpu_scan_error(scn));
-                    qfail = true;
-                }
-                std::vector<ccsx_scan_piece> pcs;
-                uint64_t h0 = 0;
-                for (size_t i = 0; i < sin.size() && !qfail; ++i) {
-                    Zmw &z = ch.zs[who[i]];
-                    const uint32_t n = (uint32_t)z.ccs.size();
-                    uint64_t h1 = h0;
-                    while (h1 < nhits && hits[h1].read == i) ++h1;
-                    const ccsx_scan_hit *h = hits + h0;
-                    const uint64_t nh = h1 - h0;
-                    h0 = h1;
-                    char num[160];
-                    const std::string name = z.movie + "/" + z.hole + "/ccs";
-                    if (fp_hit)
-                        for (uint64_t k = 0; k < nh; ++k) {
-                            snprintf(num, sizeof num, "\t%c\t%u\t%u\t%d\t%u\n", h[k].orient ? '-' : '+', h[k].start, h[k].end,
-                                     h[k].score, ad_len[h[k].adapter]);
-                            z.scan_rows += name + '\t' + std::to_string(n) + '\t' + ad_names[h[k].adapter] + num;
-                        }
-                    if (fp_pcs) {
-                        const int64_t np = ccsx_scan_cut(h, nh, n, (uint32_t)ad_min_piece, nullptr, 0);
-                        pcs.resize((size_t)np);
-                        ccsx_scan_cut(h, nh, n, (uint32_t)ad_min_piece, pcs.data(), (uint64_t)np);
-                        auto flank = [&](int32_t k) {
-                            return k < 0 ? std::string(".") : ad_names[h[k].adapter] + (h[k].orient ? '-' : '+');
-                        };
-                        for (const ccsx_scan_piece &p : pcs) {
-                            std::string &s = z.pieces;
-                            snprintf(num, sizeof num, "/%u_%u", p.b, p.e);
-                            s += fastq ? '@' : '>';
-                            s += name + num + " la=" + flank(p.left) + " ra=" + flank(p.right) + '\n';
-                            s.append(z.ccs, p.b, p.e - p.b);
-                            s += '\n';
-                            if (fastq) {
-                                s += "+\n";
-                                s.append(z.qual, p.b, p.e - p.b);
-                                s += '\n';
-                            }
-                        }
-                    }
-                }
-            }
+            // false from here on: an output of the batch is missing (a context error)
+            for (size_t i = 0; i < f.b.idx.size() && ok; ++i) ok = gather_zmw(opt, ctx[w], f, i, ch.zs[f.b.idx[i]]);
+            ok = ok && (!st.pol || polish_batch(st, ctx[w], f));
+            ok = ok && (!st.bc || demux_batch(st, f));
+            ok = ok && (!st.scn || scan_batch(st, f));
         }
-        if ((qfail || (r != 0 && r != -2)) && !fatal.exchange(true)) {
-            std::lock_guard<std::mutex> g(err_m);
+        if (!ok && !fatal.exchange(true)) {
+            std::lock_guard<std::mutex> g(st.err_m);
             fprintf(stderr, "[ccsx] device context %d: %s\n", w, r == -9 ? "injected fatal error (test hook)" : ccsx_gpu_error(ctx[w]));
         }
         if (timing)
@@ -1327,10 +1132,10 @@ int main(int argc, char **argv)
             int l = 0;
             while (!fatal && (l = rd->next(zr)) >= 0) {
                 for (const auto &rc : zr.recs) ch->input_hi = std::max(ch->input_hi, rc.seq + rc.span);
-                if (l < min_fulllen_count + 2) continue;
+                if (l < opt.min_fulllen_count + 2) continue;
                 const uint64_t total = zr.total();
-                if (total > (uint64_t)max_subread_len || total < (uint64_t)min_subread_len) continue;
-                if (have_holes && hole_set.count(zr.hole)) continue;
+                if (total > (uint64_t)opt.max_subread_len || total < (uint64_t)opt.min_subread_len) continue;
+                if (opt.have_holes && opt.hole_set.count(zr.hole)) continue;
                 zs.emplace_back();
                 zs.back().ref = std::move(zr);
                 size_t lim = chunk_size ? chunk_size : chunk_first.load();
@@ -1396,27 +1201,29 @@ int main(int argc, char **argv)
             ccsx_gpu_set_prealloc(ctx[i], 1);
             if (verbose > 2 && split_subread) ccsx_gpu_set_bp_log(ctx[i], 1);
             if (fastq) ccsx_gpu_set_quality(ctx[i], 1);
-            if (fp_rep) ccsx_gpu_set_pass_stats(ctx[i], 1);
-            if (fp_paf || fp_pol) ccsx_gpu_set_base_map(ctx[i], 1);
-            if (fp_site) ccsx_gpu_set_pileup(ctx[i], 1);
-            if (fp_kin) ccsx_gpu_set_kinetics(ctx[i], 1);
-            if (fp_str) ccsx_gpu_set_by_strand(ctx[i], 1);
+            if (opt.has(kPass)) ccsx_gpu_set_pass_stats(ctx[i], 1);
+            if (opt.has(kPaf) || opt.has(kPolished)) ccsx_gpu_set_base_map(ctx[i], 1);
+            if (opt.has(kSites)) ccsx_gpu_set_pileup(ctx[i], 1);
+            if (opt.has(kSam)) ccsx_gpu_set_kinetics(ctx[i], 1);
+            if (opt.has(kStrands)) ccsx_gpu_set_by_strand(ctx[i], 1);
             if ((kcfg >= 0 && ccsx_gpu_set_kernel_cfg(ctx[i], kcfg) != 0) ||
                 (wg_cap > 0 && ccsx_gpu_set_wg_cap(ctx[i], (uint32_t)wg_cap) != 0) ||
                 (read_cap > 0 && ccsx_gpu_set_shred_read_cap(ctx[i], (uint32_t)read_cap) != 0) ||
                 (mem_frac > 0.f && ccsx_gpu_set_mem_frac(ctx[i], mem_frac) != 0))
                 die("invalid CCSX_KCFG / CCSX_WG_PER_CU / CCSX_SHRED_READ_CAP / CCSX_MEM_FRAC");
         }
-        if (fp_pol && ccsx_gpu_polish_open(0, 0, &pol) != 0) die("cannot open the polisher context");
-        if (bc_path) {
-            if (ccsx_gpu_bc_open(0, 0, &bc) != 0) die("cannot open the demultiplexer context");
-            if (ccsx_gpu_bc_set(bc, bc_seqs.data(), bc_off.data(), bc_len.data(), (uint32_t)bc_len.size(), (uint32_t)bc_window) != 0)
-                die(ccsx_gpu_bc_error(bc));
+        if (opt.has(kPolished) && ccsx_gpu_polish_open(0, 0, &st.pol) != 0) die("cannot open the polisher context");
+        if (opt.bc_path) {
+            const ccsx_rec::SeqSet &b = opt.barcodes;
+            if (ccsx_gpu_bc_open(0, 0, &st.bc) != 0) die("cannot open the demultiplexer context");
+            if (ccsx_gpu_bc_set(st.bc, b.seqs.data(), b.off.data(), b.len.data(), b.size(), (uint32_t)opt.bc_window) != 0)
+                die(ccsx_gpu_bc_error(st.bc));
         }
-        if (ad_path) {
-            if (ccsx_gpu_scan_open(0, 0, &scn) != 0) die("cannot open the scanner context");
-            if (ccsx_gpu_scan_set(scn, ad_seqs.data(), ad_off.data(), ad_len.data(), (uint32_t)ad_len.size(), (uint32_t)ad_min_pct) != 0)
-                die(ccsx_gpu_scan_error(scn));
+        if (opt.ad_path) {
+            const ccsx_rec::SeqSet &a = opt.adapters;
+            if (ccsx_gpu_scan_open(0, 0, &st.scn) != 0) die("cannot open the scanner context");
+            if (ccsx_gpu_scan_set(st.scn, a.seqs.data(), a.off.data(), a.len.data(), a.size(), (uint32_t)opt.ad_min_pct) != 0)
+                die(ccsx_gpu_scan_error(st.scn));
         }
         // pipelined: batches of at most ~95 % of a slot (ccsx_gpu_slot_bytes),
         // so a submitted batch always fits one launch
@@ -1474,25 +1281,9 @@ int main(int argc, char **argv)
                                 z.seg_len.size(), z.rq, z.ccs.c_str(), z.qual.c_str());
                     else
                         fprintf(fp_out, ">%s/%s/ccs\n%s\n", z.movie.c_str(), z.hole.c_str(), z.ccs.c_str());
-                    if (fp_rep)
-                        for (size_t k = 0; k < z.pst.size(); ++k) {
-                            const ccsx_pass_stat &p = z.pst[k];
-                            fprintf(fp_rep, "%s/%s/ccs\t%zu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%.6f\n", z.movie.c_str(),
-                                    z.hole.c_str(), k, z.seg_off[k], z.seg_len[k], p.match, p.mismatch, p.ins, p.del, p.cbeg,
-                                    p.cend, ccsx_pass_identity(&p));
-                        }
-                    if (fp_paf) fwrite(z.paf.data(), 1, z.paf.size(), fp_paf);
-                    if (fp_site) fwrite(z.sites.data(), 1, z.sites.size(), fp_site);
-                    if (fp_str) fwrite(z.strands.data(), 1, z.strands.size(), fp_str);
-                    if (fp_pol) fwrite(z.polished.data(), 1, z.polished.size(), fp_pol);
-                    if (fp_dmx) fwrite(z.demux.data(), 1, z.demux.size(), fp_dmx);
-                    if (fp_bcr) fwrite(z.demux_row.data(), 1, z.demux_row.size(), fp_bcr);
-                    if (fp_hit) fwrite(z.scan_rows.data(), 1, z.scan_rows.size(), fp_hit);
-                    if (fp_pcs) fwrite(z.pieces.data(), 1, z.pieces.size(), fp_pcs);
-                    if (fp_kin) {
-                        if (!z.kin_arrays) ++nokin;
-                        fwrite(z.kinline.data(), 1, z.kinline.size(), fp_kin);
-                    }
+                    for (int k = 0; k < kNumOutputs; ++k)
+                        if (outs[k].fp) fwrite(z.side[k].data(), 1, z.side[k].size(), outs[k].fp);
+                    if (opt.has(kSam) && !z.kin_arrays) ++nokin;
                 }
             }
             if (timing) fprintf(stderr, "[ccsx] chunk %zu written at %.0f ms\n", ch->id, now_ms());
@@ -1518,7 +1309,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "[ccsx] CCSX_GPU_STRAND: cannot open the device aligner; preparing on the host\n");
             }
         }
-        prepare_chunk(*ch, nthreads, verbose, fp_kin != nullptr, aln, timing);
+        prepare_chunk(*ch, nthreads, verbose, opt.has(kSam), aln, timing);
         // the chunk's bases are in its arena: its input pages go (a mapped
         // file is unmapped behind the reader instead of all at the exit)
         if (input_release) rd->release(ch->input_hi);
@@ -1574,16 +1365,8 @@ int main(int argc, char **argv)
         // or the last chunk; process exit releases both
         // a failed final write (ENOSPC, EPIPE on a FIFO) must not exit 0
         bool werr = fp_out != stdout && (ferror(fp_out) || fclose(fp_out) != 0);
-        if (fp_rep) werr = (ferror(fp_rep) || fclose(fp_rep) != 0) || werr;
-        if (fp_paf) werr = (ferror(fp_paf) || fclose(fp_paf) != 0) || werr;
-        if (fp_site) werr = (ferror(fp_site) || fclose(fp_site) != 0) || werr;
-        if (fp_kin) werr = (ferror(fp_kin) || fclose(fp_kin) != 0) || werr;
-        if (fp_str) werr = (ferror(fp_str) || fclose(fp_str) != 0) || werr;
-        if (fp_pol) werr = (ferror(fp_pol) || fclose(fp_pol) != 0) || werr;
-        if (fp_dmx) werr = (ferror(fp_dmx) || fclose(fp_dmx) != 0) || werr;
-        if (fp_bcr) werr = (ferror(fp_bcr) || fclose(fp_bcr) != 0) || werr;
-        if (fp_hit) werr = (ferror(fp_hit) || fclose(fp_hit) != 0) || werr;
-        if (fp_pcs) werr = (ferror(fp_pcs) || fclose(fp_pcs) != 0) || werr;
+        for (Output *f = outs; f < outs + kNumOutputs; ++f)
+            if (f->fp) werr = (ferror(f->fp) || fclose(f->fp) != 0) || werr;
         werr = (ferror(stdout) || fflush(stdout) != 0) || werr;  // (-v >= 3 breakpoint lines go to stdout)
         if (werr) fprintf(stderr, "[ccsx] error writing the output: %s\n", strerror(errno));
         if (getenv("CCSX_EXIT_CLOSE")) {  // measurement: the teardown steps the exit skips, timed
@@ -1612,32 +1395,24 @@ int main(int argc, char **argv)
                     (unsigned long long)cells_total.load(),
                     std::chrono::duration<double>(std::chrono::system_clock::now().time_since_epoch()).count());
         if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
-        if (fp_kin) fprintf(stderr, "[ccsx] %zu ZMWs without kinetics: their -k lines carry no fi/fp/ri/rp arrays\n", nokin);
+        if (opt.has(kSam)) fprintf(stderr, "[ccsx] %zu ZMWs without kinetics: their -k lines carry no fi/fp/ri/rp arrays\n", nokin);
         fflush(stderr);
         std::_Exit(werr ? 1 : 0);
     }
     for (auto &t : workers) t.join();
     for (auto *x : ctx) ccsx_gpu_close(x);
     ccsx_gpu_aln_close(aln);
-    ccsx_gpu_polish_close(pol);
-    ccsx_gpu_bc_close(bc);
-    ccsx_gpu_scan_close(scn);
+    ccsx_gpu_polish_close(st.pol);
+    ccsx_gpu_bc_close(st.bc);
+    ccsx_gpu_scan_close(st.scn);
     reap.push(nullptr);
     reaper.join();
     if (timing) fprintf(stderr, "[ccsx] output done at %.0f ms, contexts closed at %.0f ms\n", tw, now_ms());
     rd.reset();
     if (fp_out != stdout) (void)fclose(fp_out);
     else (void)fflush(stdout);
-    if (fp_rep) (void)fclose(fp_rep);
-    if (fp_paf) (void)fclose(fp_paf);
-    if (fp_site) (void)fclose(fp_site);
-    if (fp_kin) (void)fclose(fp_kin);
-    if (fp_str) (void)fclose(fp_str);
-    if (fp_pol) (void)fclose(fp_pol);
-    if (fp_dmx) (void)fclose(fp_dmx);
-    if (fp_bcr) (void)fclose(fp_bcr);
-    if (fp_hit) (void)fclose(fp_hit);
-    if (fp_pcs) (void)fclose(fp_pcs);
+    for (Output *f = outs; f < outs + kNumOutputs; ++f)
+        if (f->fp) (void)fclose(f->fp);
     if (nfail) fprintf(stderr, "[ccsx] %zu ZMWs had no CCS (device status, see above)\n", nfail);
     return fatal ? 1 : 0;
 }
