@@ -118,11 +118,13 @@ def build_product(verbose: bool = False) -> str:
         os.path.join(CSRC, "ccsx_polish.hip"),  # the polisher's kernels, compiled once
         os.path.join(CSRC, "ccsx_barcode.hip"),  # the demultiplexer's kernel, compiled once
         os.path.join(CSRC, "ccsx_scan.hip"),  # the adapter scanner's kernel, compiled once
+        os.path.join(CSRC, "ccsx_ref.hip"),  # the reference mapper's vote kernel, compiled once
         os.path.join(CSRC, "ccsx_gpu.cpp"),
         os.path.join(CSRC, "ccsx_align.cpp"),
         os.path.join(CSRC, "ccsx_polish.cpp"),
         os.path.join(CSRC, "ccsx_barcode.cpp"),
         os.path.join(CSRC, "ccsx_scan.cpp"),
+        os.path.join(CSRC, "ccsx_ref.cpp"),
         os.path.join(CSRC, "bspoa_gpu.cpp"),
         os.path.join(CSRC, "host", "prepare.cpp"),
         os.path.join(CSRC, "host", "pairwise.cpp"),
@@ -138,6 +140,7 @@ def build_product(verbose: bool = False) -> str:
         os.path.join(CSRC, "host", "polish.cpp"),
         os.path.join(CSRC, "host", "barcode.cpp"),
         os.path.join(CSRC, "host", "scan.cpp"),
+        os.path.join(CSRC, "host", "refmap.cpp"),
     ]
     common = ["-O3", "-std=c++17", "-fPIC", "-I" + INC, "-I" + CSRC, "-I" + os.path.join(CSRC, "host")]
     # the kernel's per-ZMW chains are latency-bound: the ILP-maximising machine
@@ -151,11 +154,11 @@ def build_product(verbose: bool = False) -> str:
     # objects take minutes each; host objects seconds)
     objs, jobs = [], []
     for s in srcs:
-        if s.endswith(("ccsx_align.hip", "ccsx_polish.hip", "ccsx_barcode.hip", "ccsx_scan.hip")):
+        if s.endswith(("ccsx_align.hip", "ccsx_polish.hip", "ccsx_barcode.hip", "ccsx_scan.hip", "ccsx_ref.hip")):
             o = os.path.join(OBJ, os.path.basename(s) + ".o")
             objs.append(o)
-            # (ccsx_barcode.h and ccsx_scan.h take §1's coding from ccsx_polish.h)
-            if _stale(o, [s, s[:-4] + ".h", os.path.join(CSRC, "ccsx_polish.h")] + khdrs[:1]):
+            # (ccsx_barcode.h and ccsx_scan.h take §1's coding from ccsx_polish.h; ccsx_ref.h the band's job from ccsx_align.h)
+            if _stale(o, [s, s[:-4] + ".h", os.path.join(CSRC, "ccsx_polish.h"), os.path.join(CSRC, "ccsx_align.h")] + khdrs[:1]):
                 jobs.append([hipcc, "-x", "hip", "--offload-arch=" + ARCH] + common + ["-c", s, "-o", o])
             continue
         if s.endswith(".hip"):

@@ -27,7 +27,7 @@ struct Job {
     uint64_t rec_off;       // words from Args::rec (qlen rows of kRowWords)
     uint32_t qlen, tlen;
     int32_t d0;
-    uint32_t pad;
+    uint32_t pad;  // the path variant: the job's first word in Args::words
 };
 
 struct Args {
@@ -36,6 +36,11 @@ struct Args {
     uint32_t *rec;
     int32_t *out;  // 10 words per job (ccsx_pairaln)
     uint32_t njobs;
+};
+
+// the path variant's (SPEC.md §18): one §11 word per query base, job by job
+struct PathArgs : Args {
+    uint32_t *words;
 };
 
 }  // namespace ccsx_aln

@@ -31,6 +31,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "ccsx_align.h"
 
 namespace ccsx_aln {
@@ -63,6 +65,7 @@ __device__ __forceinline__ int wave_max(int v) { return __builtin_amdgcn_readlan
 __device__ __forceinline__ int wave_min(int v) { return -wave_max(-v); }
 
 constexpr int kNeg = -(1 << 29);  // below every score, far from overflow
+constexpr uint32_t kMapMismatch = 0x40000000u, kMapIns = 0x80000000u;  // CCSX_MAP_MISMATCH, CCSX_MAP_INS
 constexpr int kC = kCellsPerLane;
 
 __device__ __forceinline__ uint32_t tcode(const uint8_t *t, int tlen, int j, bool lane_in_band)
@@ -72,8 +75,15 @@ __device__ __forceinline__ uint32_t tcode(const uint8_t *t, int tlen, int j, boo
     return b < 4u ? b : 4u;
 }
 
-__global__ __launch_bounds__(64) void band_align(const Args a)
+// PATH: the traceback also stores the §11 word of every query base it consumes
+// and the wave then fills the clipped ends (SPEC.md §18); PATH = false is the
+// aligner's kernel, instruction for instruction (it keeps Args: a longer
+// argument block would move the hidden arguments behind it)
+template <bool PATH>
+__global__ __launch_bounds__(64) void band_align(const std::conditional_t<PATH, PathArgs, Args> a)
 {
+    uint32_t *words = nullptr;
+    if constexpr (PATH) words = a.words;
     __shared__ uint32_t tbuf[kTbRows * kRowWords];
     const int lane = (int)threadIdx.x;
     const bool in_band = lane < kBandLanes;
@@ -181,10 +191,12 @@ __global__ __launch_bounds__(64) void band_align(const Args a)
                 if (dir == 1) {
                     if (d & 4u) ++mat;
                     else ++mis;
+                    if (PATH && lane == 0) words[jb.pad + (uint32_t)i] = (uint32_t)j | (d & 4u ? 0u : kMapMismatch);
                     qb = i, tb = j;
                     --i;
                 } else if (dir == 2) {
                     ++ins;
+                    if (PATH && lane == 0) words[jb.pad + (uint32_t)i] = kMapIns | (uint32_t)(j + 1);
                     qb = i;
                     --i, ++k;
                 } else {
@@ -202,6 +214,12 @@ __global__ __launch_bounds__(64) void band_align(const Args a)
 #pragma unroll
             for (int f = 0; f < 10; ++f) a.out[(uint64_t)job * 10 + f] = res[f];
         }
+        if (PATH) {
+            // the clipped ends: before qb the words point at tb, from qe on at te
+            // (the all-zero result: at 0 throughout)
+            for (int w = lane; w < res[0]; w += 64) words[jb.pad + (uint32_t)w] = kMapIns | (uint32_t)res[2];
+            for (int w = res[1] + lane; w < qlen; w += 64) words[jb.pad + (uint32_t)w] = kMapIns | (uint32_t)res[3];
+        }
         __syncthreads();  // the next job's traceback reuses tbuf
     }
 }
@@ -210,6 +228,13 @@ __global__ __launch_bounds__(64) void band_align(const Args a)
 
 extern "C" hipError_t ccsx_launch_band_align(const ccsx_aln::Args *a, uint32_t blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(ccsx_aln::band_align, dim3(blocks), dim3(64), 0, s, *a);
+    hipLaunchKernelGGL(ccsx_aln::band_align<false>, dim3(blocks), dim3(64), 0, s, *a);
+    return hipGetLastError();
+}
+
+// the path variant (the reference mapper, ccsx_ref.cpp): a->words receives the path
+extern "C" hipError_t ccsx_launch_band_align_path(const ccsx_aln::PathArgs *a, uint32_t blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL(ccsx_aln::band_align<true>, dim3(blocks), dim3(64), 0, s, *a);
     return hipGetLastError();
 }

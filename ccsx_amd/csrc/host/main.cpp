@@ -119,7 +119,7 @@ private:
 // The side files, in the order they are opened.  A further file is a row
 // here, its formatter (records.h), its call in gather_zmw or a stage, and its
 // line in usage()
-enum { kPass, kPaf, kSites, kSam, kStrands, kPolished, kDemux, kDemuxRows, kHits, kPieces, kNumOutputs };
+enum { kPass, kPaf, kSites, kSam, kStrands, kPolished, kDemux, kDemuxRows, kHits, kPieces, kRefPaf, kNumOutputs };
 struct Output {
     char opt;
     const char *path;    // null: not asked for
@@ -134,7 +134,8 @@ struct Options {
                                {'s', nullptr, nullptr, nullptr},               {'k', nullptr, nullptr, ccsx_rec::kSamHeader},
                                {'b', nullptr, nullptr, nullptr},               {'p', nullptr, nullptr, nullptr},
                                {'d', nullptr, nullptr, nullptr},               {'D', nullptr, nullptr, ccsx_rec::kDemuxHeader},
-                               {'i', nullptr, nullptr, ccsx_rec::kHitHeader},  {'S', nullptr, nullptr, nullptr}};
+                               {'i', nullptr, nullptr, ccsx_rec::kHitHeader},  {'S', nullptr, nullptr, nullptr},
+                               {'g', nullptr, nullptr, nullptr}};
     bool has(int k) const { return out[k].path != nullptr; }
     const char *bc_path = nullptr;  // -B
     ccsx_rec::SeqSet barcodes;
@@ -142,6 +143,10 @@ struct Options {
     const char *ad_path = nullptr;  // -I
     ccsx_rec::SeqSet adapters;
     int ad_min_pct = 75, ad_min_piece = 50;  // -E -e
+    const char *ref_path = nullptr;  // -G
+    ccsx_rec::SeqSet refs;
+    ccsx_ref_set *ref_set = nullptr;  // the checked and indexed set (ccsx_ref_set_make)
+    int ref_min_pct = 75, ref_min_aln = 50;  // -Y -y
     std::unordered_set<std::string> hole_set;  // -X
     bool have_holes = false;
     const char *in_path = "-";
@@ -221,6 +226,10 @@ int usage()
             "-S     <file>  With -I: the reads cut at their hits (fasta, fastq with -q): the pieces as <name>/<b>_<e> la=<adapter><+|-> ra=<adapter><+|-> (. at a read's end) \n"
             "-E     <int>   With -I: a place is a hit if its score is at least this percentage of the adapter's length, 1..100. [75] \n"
             "-e     <int>   With -I: the shortest piece -S writes. [50] \n"
+            "-G     <file>  Reference FASTA (1..64 sequences of at least 13 letters, at most 1048576 in all; N allowed): every CCS read is mapped on the GPU to the sequence and strand its 13-mers vote for, and aligned there in a band of +-256 diagonals \n"
+            "-g     <file>  With -G: the reads' alignments (PAF, cg:Z: with =/X/I/D; AS:i: score, sv:i: / s2:i: the seed votes of the target and of the best other one), one line per reported read \n"
+            "-Y     <int>   With -G: a read is reported if its matches are at least this percentage of its alignment's columns, 0..100. [75] \n"
+            "-y     <int>   With -G: ... and the alignment has at least this many columns. [50] \n"
             "-k     <file>  Consensus kinetics (unaligned SAM; BAM input only): per CCS read its bases, np/fn/rn and, from the subreads' ip/pw tags, the per-strand mean inter-pulse duration and pulse width per base as fi/fp/ri/rp B:C arrays \n"
             "-X\t\t<str>   Exclude ZMWs from output file,a comma-separated list of ID \n"
             "-j     <int>   Number of CPU threads for subread preparation. [1] \n"
@@ -571,8 +580,9 @@ int parse_options(int argc, char **argv, Options &o)
 {
     int c;
     bool ad_opts = false;  // -E or -e given
+    bool ref_opts = false;  // -Y or -y given
     std::string xbuf;      // -X: kputs-appended, ksplit in place (exclude_holes)
-    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:I:i:S:E:e:")) != -1) {
+    while ((c = getopt(argc, argv, "hm:M:c:j:X:PAvqr:a:s:k:b:p:B:d:D:W:T:L:I:i:S:E:e:G:g:Y:y:")) != -1) {
         switch (c) {
         case 'm': o.min_subread_len = atoi(optarg); break;
         case 'M': o.max_subread_len = atoi(optarg); break;
@@ -586,6 +596,9 @@ int parse_options(int argc, char **argv, Options &o)
         case 'I': o.ad_path = optarg; break;
         case 'E': o.ad_min_pct = atoi(optarg), ad_opts = true; break;
         case 'e': o.ad_min_piece = atoi(optarg), ad_opts = true; break;
+        case 'G': o.ref_path = optarg; break;
+        case 'Y': o.ref_min_pct = atoi(optarg), ref_opts = true; break;
+        case 'y': o.ref_min_aln = atoi(optarg), ref_opts = true; break;
         case 'X':  // main.c:772-782
             o.have_holes = true;
             o.hole_set = exclude_holes(xbuf, optarg);
@@ -605,6 +618,28 @@ int parse_options(int argc, char **argv, Options &o)
             if (f == o.out + kNumOutputs) return usage();
             f->path = optarg;
         }
+        }
+    }
+    // -G first: its file is checked before anything else is opened
+    if ((o.has(kRefPaf) || ref_opts) && !o.ref_path) {
+        fprintf(stderr, "Error! -g, -Y and -y need a reference file (-G)\n");
+        return 1;
+    }
+    if (o.ref_path) {
+        if (o.ref_min_pct < 0 || o.ref_min_pct > 100) {
+            fprintf(stderr, "Error! -Y=[%d] (0..100) !\n", o.ref_min_pct);
+            return 1;
+        }
+        if (o.ref_min_aln < 0) {
+            fprintf(stderr, "Error! -y=[%d] (>=0) !\n", o.ref_min_aln);
+            return 1;
+        }
+        const ccsx_rec::SeqSet &g = o.refs;
+        if (o.refs.read(o.ref_path)) o.ref_set = ccsx_ref_set_make(g.seqs.data(), g.off.data(), g.len.data(), g.size());
+        if (!o.ref_set) {
+            fprintf(stderr, "Error! %s is not a reference file: 1..64 records of at least 13 letters, at most 1048576 in all\n",
+                    o.ref_path);
+            return 1;
         }
     }
     if (o.has(kSam) && !o.isbam) {
@@ -678,6 +713,9 @@ struct Stages {
     // next call, so a worker keeps scan_m from its call until it has used them
     ccsx_scan_ctx *scn = nullptr;
     std::mutex scan_m;
+    // -G: the one mapper context, on the first GPU (its calls copy their results out)
+    ccsx_ref_ctx *ref = nullptr;
+    std::mutex ref_m;
     std::mutex err_m;  // stderr
 };
 
@@ -842,6 +880,35 @@ bool scan_batch(Stages &st, const Flight &f)
             ccsx_rec::piece_records(z.side[kPieces], o.fastq, z.name, z.ccs, z.qual, hits + h0, h1 - h0, o.adapters,
                                     (uint32_t)o.ad_min_piece);
         h0 = h1;
+    }
+    return true;
+}
+
+// -G: the batch's CCS reads are mapped here; then the report rule and the PAF lines
+bool map_batch(Stages &st, const Flight &f)
+{
+    const Options &o = st.opt;
+    std::vector<ccsx_scan_in> rin;
+    const std::vector<size_t> who = reads_with_ccs(f, rin);
+    if (rin.empty()) return true;
+    std::vector<ccsx_ref_rec> recs(rin.size());
+    std::vector<uint32_t> words;
+    if (o.has(kRefPaf)) {
+        size_t total = 0;
+        for (const ccsx_scan_in &r : rin) total += r.len;
+        words.resize(total);
+    }
+    {
+        std::lock_guard<std::mutex> g(st.ref_m);
+        if (ccsx_gpu_ref_map(st.ref, rin.data(), rin.size(), recs.data(), o.has(kRefPaf) ? words.data() : nullptr, nullptr) != 0)
+            return stage_failed(st, "mapper", ccsx_gpu_ref_error(st.ref));
+    }
+    size_t at = 0;
+    for (size_t i = 0; i < rin.size() && o.has(kRefPaf); ++i) {
+        Zmw &z = f.b.chunk->zs[f.b.idx[who[i]]];
+        if (ccsx_ref_pass(&recs[i], o.ref_min_aln, o.ref_min_pct))
+            ccsx_rec::ref_line(z.side[kRefPaf], z.name, rin[i].len, recs[i], words.data() + at, o.refs);
+        at += rin[i].len;
     }
     return true;
 }
@@ -1012,6 +1079,7 @@ int main(int argc, char **argv)
             ok = ok && (!st.pol || polish_batch(st, ctx[w], f));
             ok = ok && (!st.bc || demux_batch(st, f));
             ok = ok && (!st.scn || scan_batch(st, f));
+            ok = ok && (!st.ref || map_batch(st, f));
         }
         if (!ok && !fatal.exchange(true)) {
             std::lock_guard<std::mutex> g(st.err_m);
@@ -1225,6 +1293,10 @@ int main(int argc, char **argv)
             if (ccsx_gpu_scan_set(st.scn, a.seqs.data(), a.off.data(), a.len.data(), a.size(), (uint32_t)opt.ad_min_pct) != 0)
                 die(ccsx_gpu_scan_error(st.scn));
         }
+        if (opt.ref_path) {
+            if (ccsx_gpu_ref_open(0, 0, &st.ref) != 0) die("cannot open the mapper context");
+            if (ccsx_gpu_ref_set(st.ref, opt.ref_set) != 0) die(ccsx_gpu_ref_error(st.ref));
+        }
         // pipelined: batches of at most ~95 % of a slot (ccsx_gpu_slot_bytes),
         // so a submitted batch always fits one launch
         if (async && ccsx_gpu_slot_bytes(ctx[0], &slot_bytes) != 0) die(ccsx_gpu_error(ctx[0]));
@@ -1405,6 +1477,8 @@ int main(int argc, char **argv)
     ccsx_gpu_polish_close(st.pol);
     ccsx_gpu_bc_close(st.bc);
     ccsx_gpu_scan_close(st.scn);
+    ccsx_gpu_ref_close(st.ref);
+    ccsx_ref_set_free(opt.ref_set);
     reap.push(nullptr);
     reaper.join();
     if (timing) fprintf(stderr, "[ccsx] output done at %.0f ms, contexts closed at %.0f ms\n", tw, now_ms());

@@ -82,8 +82,17 @@ int ccsx_pairwise_seed(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32
 // ccsx_align.hip, reproduces field for field)
 ccsx_pairaln ccsx_pairwise_band(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t d0_in)
 {
+    return ccsx_pairwise_band_path(q, qlen, t, tlen, d0_in, nullptr);
+}
+
+// the same, and the path as one SPEC.md §11 word per query base (§18)
+ccsx_pairaln ccsx_pairwise_band_path(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t d0_in,
+                                     uint32_t *words)
+{
     ccsx_pairaln r;
     memset(&r, 0, sizeof r);
+    if (words)
+        for (uint32_t w = 0; w < qlen; ++w) words[w] = CCSX_MAP_INS;
     const int64_t d0 = d0_in;
     // 2. banded local alignment over diagonals [d0 - kHalfBand, d0 + kHalfBand]
     const int BW = 2 * kHalfBand + 1;
@@ -123,12 +132,15 @@ ccsx_pairaln ccsx_pairwise_band(const uint8_t *q, uint32_t qlen, const uint8_t *
         if (dir == 0) break;
         const int64_t j = i + d0 - kHalfBand + k;
         if (dir == 1) {
-            if (q[i] < 4 && q[i] == t[j]) ++r.mat;
+            const bool same = q[i] < 4 && q[i] == t[j];
+            if (same) ++r.mat;
             else ++r.mis;
+            if (words) words[i] = (uint32_t)j | (same ? 0u : CCSX_MAP_MISMATCH);
             r.qb = (int32_t)i, r.tb = (int32_t)j;
             --i;
         } else if (dir == 2) {
             ++r.ins;  // query base not in target
+            if (words) words[i] = CCSX_MAP_INS | (uint32_t)(j + 1);
             r.qb = (int32_t)i;
             --i, ++k;
         } else {
@@ -139,6 +151,11 @@ ccsx_pairaln ccsx_pairwise_band(const uint8_t *q, uint32_t qlen, const uint8_t *
         if (i < 0 || k < 0 || k >= BW) break;
     }
     r.aln = r.mat + r.mis + r.ins + r.del;
+    if (words) {
+        // the clipped ends lie before the first and after the last aligned base
+        for (int32_t w = 0; w < r.qb; ++w) words[w] = CCSX_MAP_INS | (uint32_t)r.tb;
+        for (uint32_t w = (uint32_t)r.qe; w < qlen; ++w) words[w] = CCSX_MAP_INS | (uint32_t)r.te;
+    }
     return r;
 }
 

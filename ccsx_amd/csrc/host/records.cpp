@@ -221,4 +221,24 @@ void piece_records(std::string &s, bool fastq, const std::string &name, const st
     }
 }
 
+void ref_line(std::string &s, const std::string &name, uint32_t n, const ccsx_ref_rec &r, const uint32_t *words,
+              const SeqSet &refs)
+{
+    ccsx_map_aln a;
+    const long c = ccsx_map_cigar(words, n, &a, nullptr, 0);
+    if (c < 0 || r.g < 0) return;
+    const uint32_t qb = (uint32_t)r.a.qb, qe = (uint32_t)r.a.qe;
+    char num[256];
+    snprintf(num, sizeof num, "\t%u\t%u\t%u\t%c\t", n, r.o ? n - qe : qb, r.o ? n - qb : qe, r.o ? '-' : '+');
+    s += name + num + refs.names[(size_t)r.g];
+    snprintf(num, sizeof num, "\t%u\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tsv:i:%d\ts2:i:%d\tcg:Z:", refs.len[(size_t)r.g], r.a.tb, r.a.te,
+             r.a.mat, r.a.aln, r.a.score, r.votes, r.votes2);
+    s += num;
+    const size_t at = s.size();
+    s.resize(at + (size_t)c + 1);
+    (void)ccsx_map_cigar(words, n, &a, &s[at], (size_t)c + 1);
+    s.resize(at + (size_t)c);
+    s += '\n';
+}
+
 }  // namespace ccsx_rec

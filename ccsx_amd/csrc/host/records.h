@@ -81,4 +81,9 @@ void hit_rows(std::string &s, const std::string &name, uint32_t n, const ccsx_sc
 void piece_records(std::string &s, bool fastq, const std::string &name, const std::string &ccs, const std::string &qual,
                    const ccsx_scan_hit *hits, uint64_t nhits, const SeqSet &adapters, uint32_t min_piece);
 
+// -g (section 18): the PAF line of a reported read of n bases from its record
+// and the words of its path; query coordinates on the read as written
+void ref_line(std::string &s, const std::string &name, uint32_t n, const ccsx_ref_rec &r, const uint32_t *words,
+              const SeqSet &refs);
+
 }  // namespace ccsx_rec

@@ -40,7 +40,9 @@ EXPORTS = {
                    "ccsx_gpu_bc_open", "ccsx_gpu_bc_close", "ccsx_gpu_bc_error", "ccsx_gpu_bc_set", "ccsx_gpu_bc_score",
                    "ccsx_gpu_bc_stats",
                    "ccsx_gpu_scan_open", "ccsx_gpu_scan_close", "ccsx_gpu_scan_error", "ccsx_gpu_scan_set", "ccsx_gpu_scan",
-                   "ccsx_gpu_scan_tracks", "ccsx_gpu_scan_tile", "ccsx_gpu_scan_stats"],
+                   "ccsx_gpu_scan_tracks", "ccsx_gpu_scan_tile", "ccsx_gpu_scan_stats",
+                   "ccsx_gpu_ref_open", "ccsx_gpu_ref_close", "ccsx_gpu_ref_error", "ccsx_gpu_ref_set", "ccsx_gpu_ref_map",
+                   "ccsx_gpu_ref_vote_cap", "ccsx_gpu_ref_stats"],
     "ccsx_bspoa.h": ["init_bspoa", "beg_bspoa", "push_bspoa", "end_bspoa", "tidy_msa_bspoa", "free_bspoa"],
     "ccsx_host.h": ["ccsx_revcomp", "ccsx_prepare", "ccsx_prepare_apply", "ccsx_pairwise", "ccsx_synth_zmw",
                     "ccsx_zmw_cost", "ccsx_partition", "ccsx_qual_phred", "ccsx_qual_rq", "ccsx_pass_identity",
@@ -48,6 +50,7 @@ EXPORTS = {
                     "ccsx_barcode_check", "ccsx_barcode_host", "ccsx_barcode_call", "ccsx_barcode_read",
                     "ccsx_barcode_set_get", "ccsx_barcode_set_free",
                     "ccsx_scan_check", "ccsx_scan_host", "ccsx_scan_start", "ccsx_scan_cut",
+                    "ccsx_pairwise_band_path", "ccsx_ref_set_make", "ccsx_ref_set_free", "ccsx_ref_host", "ccsx_ref_pass",
                     "ccsx_prepare_apply_kin", "ccsx_kin_frames", "ccsx_kin_code", "ccsx_kinetics_tags",
                     "ccsx_synth_batch_kinetics",
                     "ccsx_pairwise_seed", "ccsx_pairwise_band", "ccsx_prep_begin", "ccsx_prep_pending",
@@ -106,6 +109,11 @@ class BcCall(C.Structure):
 class ScanHit(C.Structure):
     _fields_ = [("read", C.c_uint32), ("adapter", C.c_uint32), ("orient", C.c_uint32), ("start", C.c_uint32),
                 ("end", C.c_uint32), ("score", C.c_int32)]
+
+
+class RefRec(C.Structure):
+    # g, o, d0, votes, votes2, then the ten fields of ccsx_pairaln
+    _fields_ = [("v", C.c_int32 * 15)]
 
 
 class ScanPiece(C.Structure):
@@ -308,6 +316,25 @@ def lib() -> C.CDLL:
             L.ccsx_gpu_scan_tracks.argtypes = [C.c_void_p, C.POINTER(BcIn), C.c_size_t, C.c_void_p, C.c_uint64]
             L.ccsx_gpu_scan_tile.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
             L.ccsx_gpu_scan_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
+        if hasattr(L, "ccsx_gpu_ref_map"):  # (absent from the older builds used in A/B runs)
+            L.ccsx_ref_set_make.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
+            L.ccsx_ref_set_make.restype = C.c_void_p
+            L.ccsx_ref_set_free.argtypes = [C.c_void_p]
+            L.ccsx_ref_set_free.restype = None
+            L.ccsx_ref_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(RefRec), C.c_void_p]
+            L.ccsx_ref_host.restype = C.c_int32
+            L.ccsx_ref_pass.argtypes = [C.POINTER(RefRec), C.c_int32, C.c_int32]
+            L.ccsx_ref_pass.restype = C.c_int32
+            L.ccsx_gpu_ref_open.argtypes = [C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.ccsx_gpu_ref_close.argtypes = [C.c_void_p]
+            L.ccsx_gpu_ref_close.restype = None
+            L.ccsx_gpu_ref_error.argtypes = [C.c_void_p]
+            L.ccsx_gpu_ref_error.restype = C.c_char_p
+            L.ccsx_gpu_ref_set.argtypes = [C.c_void_p, C.c_void_p]
+            L.ccsx_gpu_ref_map.argtypes = [C.c_void_p, C.POINTER(BcIn), C.c_size_t, C.POINTER(RefRec), C.c_void_p,
+                                           C.POINTER(C.c_float)]
+            L.ccsx_gpu_ref_vote_cap.argtypes = [C.c_void_p, C.c_uint32]
+            L.ccsx_gpu_ref_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         L.ccsx_synth_zmw.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p,
                                      C.POINTER(C.c_uint32), C.c_char_p]
         L.ccsx_synth_zmw.restype = C.c_uint64
@@ -1050,6 +1077,129 @@ class Scanner:
         if self._L.ccsx_gpu_scan_stats(self._ctx, st, 6) != 0:
             self._err("ccsx_gpu_scan_stats")
         return dict(zip(("reads", "slices", "sets", "candidates", "reruns", "host_reads"), (int(x) for x in st)))
+
+
+REF_FIELDS = ("g", "o", "d0", "votes", "votes2", "qb", "qe", "tb", "te", "mat", "mis", "ins", "del", "aln", "score")
+_REF_SET_ERR = "not a reference set (1..64 sequences of at least 13 letters, at most 1,048,576 letters in all)"
+
+
+def read_refs(path: str) -> list:
+    """[(name, sequence)] of a reference FASTA (ccsx_barcode_read), unchecked;
+    OSError if it cannot be opened or holds no record."""
+    return read_barcodes(path)
+
+
+class RefSet:
+    """A ccsx_ref_set (ccsx_ref_set_make); ValueError for a bad one."""
+
+    def __init__(self, refs):
+        seqs, offs, lens = _barcode_set(refs)
+        self._L = lib()
+        self.p = self._L.ccsx_ref_set_make(seqs, _p32(offs), _p32(lens), len(lens))
+        if not self.p:
+            raise ValueError(_REF_SET_ERR)
+
+    def __del__(self):
+        if getattr(self, "p", None):
+            self._L.ccsx_ref_set_free(self.p)
+            self.p = None
+
+
+def _ref_rec(r: RefRec) -> tuple:
+    return tuple(int(x) for x in r.v)
+
+
+def ref_host(refs, ccs: bytes, words: bool = True):
+    """ccsx_ref_host (SPEC.md §18) of one CCS read against the reference
+    sequences `refs` (or a RefSet made from them once): (record,
+    words); the record as a tuple in REF_FIELDS' order, the words as a uint32
+    array of the read's length (of the read in orientation o), or None."""
+    rs = refs if isinstance(refs, RefSet) else RefSet(refs)
+    ccs = bytes(ccs)
+    rec = RefRec()
+    w = np.zeros(max(len(ccs), 1), np.uint32) if words else None
+    if lib().ccsx_ref_host(rs.p, ccs, len(ccs), C.byref(rec), w.ctypes.data if words else None) != 0:
+        raise RuntimeError("ccsx_ref_host failed")
+    return _ref_rec(rec), (w[:len(ccs)] if words else None)
+
+
+def ref_pass(rec, y: int = 50, Y: int = 75) -> bool:
+    """ccsx_ref_pass: a mapped read is reported iff aln >= y and 100 mat >= Y aln."""
+    r = RefRec()
+    for k, x in enumerate(rec):
+        r.v[k] = x
+    return bool(lib().ccsx_ref_pass(C.byref(r), y, Y))
+
+
+class RefMapper:
+    """A reference mapper context on one HIP device (ccsx_gpu_ref_*): SPEC.md
+    §18's seed, band and path of many CCS reads per call against a reference
+    set; max_bytes = the most device memory its arena takes (0: the library's
+    default, 4 GiB)."""
+
+    def __init__(self, device: int = 0, max_bytes: int = 0):
+        self._L = lib()
+        self._ctx = C.c_void_p()
+        if self._L.ccsx_gpu_ref_open(device, max_bytes, C.byref(self._ctx)) != 0:
+            raise GpuError(f"cannot open a reference mapper on HIP device {device}")
+        self.vote_ms = self.band_ms = 0.0
+
+    def close(self):
+        if self._ctx:
+            self._L.ccsx_gpu_ref_close(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what: str):
+        raise GpuError(f"{what}: {self._L.ccsx_gpu_ref_error(self._ctx).decode()}")
+
+    def set(self, refs) -> None:
+        """ccsx_gpu_ref_set: the reference sequences of the calls that follow;
+        ValueError for a bad set (the earlier one stays)."""
+        rs = RefSet(refs)
+        if self._L.ccsx_gpu_ref_set(self._ctx, rs.p) != 0:
+            self._err("ccsx_gpu_ref_set")
+
+    def vote_cap(self, slots: int) -> None:
+        """ccsx_gpu_ref_vote_cap: the slots of the vote kernel's table (a power
+        of two in 64 .. 4096); a read with more distinct (target, orientation,
+        bin) keys is mapped on the host."""
+        if not 0 <= slots < 1 << 32 or self._L.ccsx_gpu_ref_vote_cap(self._ctx, slots) != 0:
+            raise ValueError("a power of two in 64 .. 4096")
+
+    def map(self, reads, words: bool = True) -> list:
+        """ccsx_gpu_ref_map on a list of CCS reads: per read (record, words) as
+        ref_host returns them; vote_ms / band_ms = the kernels' times."""
+        keep = [bytes(r) for r in reads]
+        n = len(keep)
+        arr = (BcIn * max(n, 1))()
+        for i, r in enumerate(keep):
+            arr[i].ccs, arr[i].len = r, len(r)
+        recs = (RefRec * max(n, 1))()
+        total = sum(len(r) for r in keep)
+        w = np.zeros(max(total, 1), np.uint32) if words else None
+        ms = (C.c_float * 2)()
+        if self._L.ccsx_gpu_ref_map(self._ctx, arr, n, recs, w.ctypes.data if words else None, ms) != 0:
+            self._err("ccsx_gpu_ref_map")
+        self.vote_ms, self.band_ms = float(ms[0]), float(ms[1])
+        out, at = [], 0
+        for i, r in enumerate(keep):
+            out.append((_ref_rec(recs[i]), w[at:at + len(r)].copy() if words else None))
+            at += len(r)
+        return out
+
+    def stats(self) -> dict:
+        """ccsx_gpu_ref_stats: reads, slices launched, sets, reads mapped,
+        reads whose votes overflowed, reads mapped on the host."""
+        st = (C.c_uint64 * 6)()
+        if self._L.ccsx_gpu_ref_stats(self._ctx, st, 6) != 0:
+            self._err("ccsx_gpu_ref_stats")
+        return dict(zip(("reads", "slices", "sets", "mapped", "overflows", "host_reads"), (int(x) for x in st)))
 
 
 class Polisher:

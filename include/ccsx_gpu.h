@@ -603,6 +603,52 @@ int ccsx_gpu_scan_tracks(ccsx_scan_ctx *ctx, const ccsx_scan_in *reads, size_t n
 int ccsx_gpu_scan_tile(uint32_t rows, uint32_t *TC, uint32_t *WU);
 int ccsx_gpu_scan_stats(const ccsx_scan_ctx *ctx, uint64_t *stats, uint32_t n);
 
+/* The reference mapper (SPEC.md §18 on the device, ccsx_ref.hip and the path
+ * variant of ccsx_align.hip): every CCS read is seeded against every sequence
+ * of a reference set in both orientations by the 13-mer diagonal vote (§8
+ * step 1), the winning (target, orientation) is aligned in the ±256 band (§8
+ * steps 2-3), and the alignment's path comes back as one §11 word per base of
+ * the oriented read.  Every record and word equals ccsx_ref_host's
+ * (include/ccsx_host.h).
+ *
+ * ccsx_ref_rec: g = the target's index (-1: unmapped, every other field 0),
+ * o = 0 the read as given / 1 its reverse complement, d0 = the band's centre
+ * diagonal, votes = the winning pair's vote count, votes2 = the largest count
+ * of a pair with another target (0: none), a = the band's ten fields on the
+ * oriented read.
+ *
+ * A mapper context is separate from every other context: its own stream, the
+ * set (target codes, the sorted 13-mer table and its directory) on the device,
+ * one arena of at most max_bytes (0 = 4 GiB) and pinned staging; calls are
+ * serialised.  ccsx_gpu_ref_set takes a set made by ccsx_ref_set_make (the
+ * context copies what it needs; NULL is refused and the earlier set stays).
+ * ccsx_gpu_ref_map: n reads (ASCII), cut in order into slices that fit the
+ * arena; per slice one copy in, the vote kernel, the band kernel, one copy
+ * out.  recs receives n records; words (may be NULL) the reads' words back to
+ * back, sum of len of them.  A read of 2^27 bases or more, one whose records
+ * no arena holds, and one whose votes overflow the vote kernel's table run
+ * ccsx_ref_host inside the call.  kernel_ms (may be NULL) receives two values:
+ * the vote kernels' and the band kernels' time by HIP events.
+ * ccsx_gpu_ref_vote_cap: the slots of the vote kernel's table, a power of two
+ * in 64 .. 4096 (the default); -1 for another value.
+ * ccsx_gpu_ref_stats: counters so far, the first min(n, 6) of: [0] reads,
+ * [1] slices launched, [2] sets, [3] reads mapped (g >= 0), [4] reads whose
+ * votes overflowed, [5] reads run on the host (the overflowed included). */
+typedef struct {
+    int32_t g, o, d0, votes, votes2;
+    ccsx_pairaln a;
+} ccsx_ref_rec;
+typedef struct ccsx_ref_set ccsx_ref_set;
+typedef struct ccsx_ref_ctx ccsx_ref_ctx;
+int ccsx_gpu_ref_open(int device, uint64_t max_bytes, ccsx_ref_ctx **ctx);
+void ccsx_gpu_ref_close(ccsx_ref_ctx *ctx);
+const char *ccsx_gpu_ref_error(const ccsx_ref_ctx *ctx);
+int ccsx_gpu_ref_set(ccsx_ref_ctx *ctx, const ccsx_ref_set *set);
+int ccsx_gpu_ref_map(ccsx_ref_ctx *ctx, const ccsx_scan_in *reads, size_t n, ccsx_ref_rec *recs, uint32_t *words,
+                     float *kernel_ms);
+int ccsx_gpu_ref_vote_cap(ccsx_ref_ctx *ctx, uint32_t slots);
+int ccsx_gpu_ref_stats(const ccsx_ref_ctx *ctx, uint64_t *stats, uint32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,32 @@ int32_t ccsx_scan_start(const char *adapter, uint32_t L, uint32_t orient, const 
 int64_t ccsx_scan_cut(const ccsx_scan_hit *hits, uint64_t nhits, uint32_t n, uint32_t Lmin, ccsx_scan_piece *pieces,
                       uint64_t cap);
 
+/* Mapping of CCS reads to a reference set (SPEC.md section 18; the device's
+ * ccsx_gpu_ref_map gives the same records and words).  A reference file is
+ * read with ccsx_barcode_read.
+ * ccsx_pairwise_band_path: ccsx_pairwise_band that also writes the path: one
+ * section 11 word per query base into words[qlen] (may be NULL): the target
+ * offset of an aligned base (CCSX_MAP_MISMATCH if the bases differ),
+ * CCSX_MAP_INS | the offset it is inserted before; CCSX_MAP_INS | tb before qb
+ * and CCSX_MAP_INS | te from qe on (CCSX_MAP_INS | 0 throughout for the
+ * all-zero result).
+ * ccsx_ref_set_make: the checked and coded set with its index, or NULL if it
+ * is not one: 1 <= G <= 64 sequences seqs + off[g] of len[g] >= 13 letters,
+ * at most 2^20 in all; ACGT in either case code 0..3, another letter 4.  The
+ * index is every 13-mer of valid bases as (kmer, g, pos), sorted, without the
+ * k-mers that occur more than 64 times in their target.
+ * ccsx_ref_host: the definition as a sequential loop for one read ccs / n
+ * (ASCII; n may be 0): writes *rec and, if words is not NULL, its n words (of
+ * the read in orientation rec->o).  Returns 0, or -1 for a NULL set or rec.
+ * ccsx_ref_pass: 1 iff the read is mapped (g >= 0), aln >= y and
+ * 100 mat >= Y aln. */
+ccsx_pairaln ccsx_pairwise_band_path(const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, int32_t d0,
+                                     uint32_t *words);
+ccsx_ref_set *ccsx_ref_set_make(const char *seqs, const uint32_t *off, const uint32_t *len, uint32_t G);
+void ccsx_ref_set_free(ccsx_ref_set *set);
+int32_t ccsx_ref_host(const ccsx_ref_set *set, const char *ccs, uint32_t n, ccsx_ref_rec *rec, uint32_t *words);
+int32_t ccsx_ref_pass(const ccsx_ref_rec *rec, int32_t y, int32_t Y);
+
 /* Synthetic PacBio-like ZMW: insert of length L drawn from
  * splitmix64(seed ^ hole), `passes` full passes on alternating strands with
  * 6% insertions / 3% deletions / 1% substitutions.  Writes the concatenated
